@@ -11,16 +11,20 @@ the kernel arguments = 2 D x 4096 transforms = D x 16 MiB of algorithmic bytes p
 launch, a run of steps opens with a forward-only launch and closes with an inverse-only one, and every transform of every
 batch is done exactly once (z == x is checked after every region).  `--depth 1` is round 4's form (one forward + one inverse
 job per launch), `--two-launch` the un-pipelined one (fz_ntt_forward, then fz_ntt_inverse: two launches of 8 MiB per step;
-by default the side leg `two_launch_step`).  The steps run as S CHAINS on S HIP streams (--streams, 2; a context + stream
+with --full the side leg `two_launch_step`).  The steps run as S CHAINS on S HIP streams (--streams, 2; a context + stream
 each, created before anything else in the process, the rotating batches dealt in contiguous shares): S launches in flight,
 which hides each launch's ramp and drain behind the other's body.  The K steps (--steps) are dealt to the chains, recorded
-into one hipGraph per chain (fz_graph_*) and replayed R times inside the timed region, R chosen so that the region lasts
->= 20 ms whatever K is.  `value` = NTTs per second over the whole job (forward and inverse each count, all chains, summed
-over all ranks); `ms_per_step` = elapsed / steps timed.  With --gpus N every rank owns its own batches (weak scaling, no
-data-path collective for the transforms).
+into hipGraphs of at most 1000 steps per chain (fz_graph_*) and replayed ONCE: the timed region is exactly the K steps.
+`value` = NTTs per second over the whole job (forward and inverse each count, all chains, summed over all ranks);
+`ms_per_step` = elapsed / K.  --dump-outputs DIR writes what the last of the K steps computed (ntt_forward.npy,
+ntt_inverse.npy; the inputs are seeded: the same arguments give the same arrays).  With --gpus N every rank owns its own
+batches (weak scaling, no data-path collective for the transforms).
 
-Output: the LAST stdout line is ONE compact strict-JSON object (< 4 KB: compact_line()); everything measured, with its
-prose, goes to gpurun_out/bench_full.json.  The compact line carries
+A plain run does only that: set up, warm up (--prewarm-ms, then the W --warmup steps), time the K steps, print the line.
+Everything else below is measured with --full only.
+
+Output: the LAST stdout line is ONE compact strict-JSON object (< 4 KB: compact_line()); with --full everything measured,
+with its prose, also goes to the --full-out file.  With --full the compact line also carries
   roofline      the dominant kernel (the 2 D-job transform launch: 8*d algorithmic bytes per transform), per launch with ONE
                 launch in flight: HIP events around a dense one-stream region of the same steps over the same rotating
                 (cold) batches / the launches in it -- the figure rocprofv3 --kernel-trace --stats reproduces (it serialises
@@ -34,8 +38,9 @@ prose, goes to gpurun_out/bench_full.json.  The compact line carries
   end_to_end    keygen / sign / aggregate / verify per second through BatchScheme, hashing included (benchmarks/benchmarks.py:37-141)
   warm_replay   the un-pipelined step re-reading ONE batch (cache-resident): the side number, never `value`
   ranks         per rank: device, PCI bus id, ranks RCCL itself counted in the communicator, RCCL version, collective self-check
-`--full` adds the side legs of tools/bench_legs.py (launch floor, fz_ntt_multi, PCIe, large-batch sweep, cold
-per-kernel table, ShardedScheme end to end) to the full file.
+and the full file the FULL_LEGS of tools/bench_legs.py (launch floor, fz_ntt_multi, PCIe, large-batch sweep, cold
+per-kernel table, ShardedScheme end to end; --no-extra-legs skips them).  At N > 1, --full also creates the exchange step's
+communicator and checks its collectives (exit codes 4 / 5).
 
 Launch: `python bench.py --gpus N` starts its own N ranks (child processes, before this process has touched a GPU) when
 WORLD_SIZE is not set; under torch.distributed.run it uses the ranks it is given.
@@ -60,7 +65,6 @@ B = 4096                       # BASELINE configs[1]
 SECPAR = 256
 MIN_REGION_MS = 20.0           # the secondary legs' timed regions (many legs: the default run stays within minutes)
 ROOFLINE_REGION_MS = 250.0     # the one-stream region `roofline.frac` / `avg_launch_us` come from (~4 600 launches of 54 us)
-HEADLINE_REGION_MS = 1000.0    # the region `value` comes from: long enough for the driver's clock and its GPU-busy sampler to see it
 NBATCH = 64                    # batches in the rotation: 3 x 64 x 4 MiB = 768 MiB, three times the 256 MB Infinity Cache
 LINE_LIMIT = 4096              # bytes of the compact line (tests/test_bench_line.py)
 
@@ -68,9 +72,18 @@ LINE_LIMIT = 4096              # bytes of the compact line (tests/test_bench_lin
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=200000, help="steps timed: the timed region is exactly these steps, once")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--full", action="store_true", help="also run the side legs of tools/bench_legs.py (full file only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and device-timestamp passes, the side legs (single-stream, "
+                         "two-launch, warm replay, sign_verify, end_to_end, the FULL_LEGS of tools/bench_legs.py), the CPU baseline, "
+                         "the communicator and its self-check at N > 1, and the full file (--full-out)")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="with --full: skip the FULL_LEGS of tools/bench_legs.py (launch floor, fz_ntt_multi, PCIe, large-batch "
+                         "sweep, cold per-kernel table, ShardedScheme end to end)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0: the forward and the inverse transforms "
+                         "of its batch) as DIR/ntt_forward.npy and DIR/ntt_inverse.npy, float64")
     ap.add_argument("--single-rank-comm", action="store_true",
                     help="N = 1 only: create a one-rank RCCL communicator so that sign_verify runs its exchange-step code path")
     ap.add_argument("--exchange-standin-us", type=int, default=0,
@@ -87,7 +100,7 @@ def parse(argv=None):
     ap.add_argument("--no-exchange-overlap", action="store_true",
                     help="sign_verify: the all-reduce on the compute stream (round 3's form) instead of a second stream")
     ap.add_argument("--headline-only", action="store_true",
-                    help="timed region + per-dispatch roofline passes only (what tools/collect_profiles.sh runs under rocprofv3)")
+                    help="with --full: timed region + per-dispatch roofline passes only (what tools/collect_profiles.sh runs under rocprofv3)")
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams (a context each) that walk disjoint shares of the rotating batches side by side: launches of "
                          "different streams overlap on the chip (1: one launch in flight at a time)")
@@ -105,8 +118,6 @@ def parse(argv=None):
                     help="bind begin/end events to every k-th dispatch in the instrumented passes (1: every dispatch carries "
                          "its own completion signal, as under rocprofv3 --kernel-trace)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the pure-Python baseline sample")
-    ap.add_argument("--region-ms", type=float, default=HEADLINE_REGION_MS,
-                    help="minimum duration of the headline's timed region: the K steps are replayed until it is reached")
     ap.add_argument("--prewarm-ms", type=float, default=150.0,
                     help="untimed run of the same steps before the W warmup steps: after idle the GPU needs tens of "
                          "milliseconds of load to reach its steady clocks")
@@ -558,7 +569,7 @@ def main():
     # device and RCCL must refuse.
     comm, collective = None, "none (single rank: no exchange step)"
     rccl_nranks, comm_error = None, None
-    if world > 1:
+    if world > 1 and args.full:                           # only sign_verify uses it: a plain run's headline has no collective
         uid = [None]
         if rank == 0:
             try:
@@ -599,7 +610,7 @@ def main():
         rccl_nranks = comm.info()[0]
         collective = f"fz_allreduce_i64 (ncclAllReduce int64 sum, C ABI), RCCL counts {rccl_nranks} rank (rehearsal)"
     try:
-        rccl_version = fusion_hip.rccl_version() if (world > 1 or comm is not None) else None
+        rccl_version = fusion_hip.rccl_version() if ((world > 1 and args.full) or comm is not None) else None
     except Exception:
         rccl_version = None
 
@@ -632,7 +643,7 @@ def main():
             dist.all_reduce(t)
             out["torch_all_reduce_i64"] = bool(np.array_equal(t.cpu().numpy(), want))
         return out
-    coll_check = collective_self_check() if (world > 1 or comm is not None) else None
+    coll_check = collective_self_check() if ((world > 1 and args.full) or comm is not None) else None
     if coll_check is not None and min_over_ranks(1.0 if all(coll_check.values()) else 0.0) < 1.0:
         sys.stderr.write(f"bench.py rank {rank}: collective self-check FAILED: {coll_check} -- exit code 5\n")
         sys.stderr.flush()
@@ -678,11 +689,13 @@ def main():
         pipe: ONE launch (fz_ntt_multi) = the forward transforms of the next g <= D batches (x_b -> y_b) + the inverse transforms
         (y_b -> z_b) of the batches the previous launch transformed forward; a run of steps opens with a forward-only launch and
         end() closes it with an inverse-only one (job tables are built once per distinct launch and kept).  two: fz_ntt_forward
-        then fz_ntt_inverse (two launches per step); warm: the same two launches on ONE batch."""
+        then fz_ntt_inverse (two launches per step); warm: the same two launches on ONE batch.  last: the rotation index of
+        the batch of the last step issued (or captured)."""
 
         def __init__(self, c, idx):
             self.ctx, self.h, self.idx, self.k, self.prev, self.tabs = c, c._h, list(idx), 0, (), {}
             self.rp = [rot_p[i] for i in self.idx]
+            self.last = None
 
         def _launch(self, new, old):
             tab = self.tabs.get((new, old))
@@ -700,12 +713,13 @@ def main():
                     new = tuple((self.k + t_) % n for t_ in range(g))
                     self.k = (self.k + g) % n
                     rc |= self._launch(new, self.prev)
-                    self.prev = new
+                    self.prev, self.last = new, self.idx[new[-1]]
                     n_steps -= g
                 return rc
             for _ in range(n_steps):
-                a_, b_, c_ = self.rp[0 if mode_ == "warm" else self.k % n]
-                self.k += 1
+                j_ = 0 if mode_ == "warm" else self.k % n
+                a_, b_, c_ = self.rp[j_]
+                self.k, self.last = self.k + 1, self.idx[j_]
                 rc |= lib.fz_ntt_forward(self.h, a_, b_, nB) | lib.fz_ntt_inverse(self.h, b_, c_, nB)
             return rc
 
@@ -733,12 +747,14 @@ def main():
             torch.cuda.synchronize(dev)
 
     def prewarm(cs, mode_, ms):
-        """untimed: keep the device busy for `ms` so the timed region starts at steady clocks (the run is closed afterwards)"""
-        t_end = time.perf_counter() + ms * 1e-3
-        while time.perf_counter() < t_end:
+        """untimed: keep the device busy for `ms` so the timed region starts at steady clocks (the run is closed afterwards).
+        Whatever `ms` is, every chain walks its whole rotation at least once (z_i defined again after a zero_())"""
+        t_end, steps_ = time.perf_counter() + ms * 1e-3, 0
+        while steps_ < max(len(c_.rp) for c_ in cs) or time.perf_counter() < t_end:
             for _ in range(12):
                 for c_ in cs:
                     c_.run(D, mode_)
+            steps_ += 12 * D
             torch.cuda.synchronize(dev)
         for c_ in cs:
             c_.end(mode_)
@@ -753,17 +769,19 @@ def main():
         torch.cuda.synchronize(dev)
         return a.elapsed_time(b_) / reps
 
-    def region(cs, mode_, K, min_ms=MIN_REGION_MS):
-        """W warmup steps, then the K steps -- dealt to the chains `cs`, every chain's share recorded into its own hipGraph
-        (M repetitions per recording for K < 1000) -- replayed for >= min_ms between two barriers.
-        -> dict(elapsed s (max over ranks), steps, per-chain event ms, per-chain steps, replays, M, shader clock)"""
+    def region(cs, mode_, K, min_ms=MIN_REGION_MS, exact=False):
+        """W warmup steps, then the K steps -- dealt to the chains `cs`, every chain's share recorded into hipGraphs of at most
+        1000 steps -- timed between two barriers.  exact (the headline): the K steps once, so that `--steps` is the number of
+        steps timed; otherwise (the side legs) replayed for >= min_ms, M repetitions per recording for K < 1000.  Step t of the
+        K is chain t % len(cs)'s.  -> dict(elapsed s (max over ranks), steps, per-chain event ms, per-chain steps, replays, M,
+        shader clock: --full only)"""
         n_c = len(cs)
         for j, c_ in enumerate(cs):
             c_.k = 0
             c_.run(args.warmup // n_c + (1 if j < args.warmup % n_c else 0), mode_)
             c_.end(mode_)
         barrier()
-        M = max(1, 1000 // K) if K < 1000 else 1
+        M = max(1, 1000 // K) if K < 1000 and not exact else 1
         # steps per chain and replay round: the M x K steps of a round dealt evenly (the shares differ by one step at most
         # whatever K is); a share is issued as launches of D steps and, when D does not divide it, one shorter launch
         share = [(M * K) // n_c + (1 if j < (M * K) % n_c else 0) for j in range(n_c)]
@@ -788,9 +806,10 @@ def main():
 
         def k_steps():
             if not args.no_graph:
-                for gl in graphs:                            # asynchronous: the chains' recordings run side by side
-                    for g in gl:
-                        g.launch()
+                for t_ in range(max(len(gl) for gl in graphs)):     # asynchronous, the chains' recordings in turn: they run side by side
+                    for gl in graphs:
+                        if t_ < len(gl):
+                            gl[t_].launch()
             else:
                 rc, grain = 0, max(1, int(per_launch_steps[mode_]))
                 for t_ in range(0, max(share), grain):
@@ -800,12 +819,14 @@ def main():
                 for c_ in cs:
                     rc |= c_.end(mode_)
                 assert rc == 0, f"launch failed: {lib.fz_last_error()}"
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        k_steps()
-        torch.cuda.synchronize(dev)
-        t_once = max(time.perf_counter() - t0, 1e-6)
-        launches = int(max_over_ranks(max(1.0, -(-min_ms * 1e-3 // t_once))))     # the same count on every rank
+        launches = 1
+        if not exact:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            k_steps()
+            torch.cuda.synchronize(dev)
+            t_once = max(time.perf_counter() - t0, 1e-6)
+            launches = int(max_over_ranks(max(1.0, -(-min_ms * 1e-3 // t_once))))     # the same count on every rank
         barrier()
         t0 = time.perf_counter()
         for c_ in cs:
@@ -816,12 +837,13 @@ def main():
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
         shader = None
-        try:                                                 # the shader clock the chip holds beside these launches (a diagnostic)
-            for _ in range(max(1, launches // 4)):
-                k_steps()
-            shader = round(ctx.diag_shader_clock(500))
-        except Exception as e:
-            shader = f"failed: {type(e).__name__}: {e}"
+        if args.full:
+            try:                                             # the shader clock the chip holds beside these launches (a diagnostic)
+                for _ in range(max(1, launches // 4)):
+                    k_steps()
+                shader = round(ctx.diag_shader_clock(500))
+            except Exception as e:
+                shader = f"failed: {type(e).__name__}: {e}"
         torch.cuda.synchronize(dev)
         for gl in graphs:
             for g in {id(g): g for g in gl}.values():
@@ -849,155 +871,24 @@ def main():
     assert torch.equal(zs, xs), "INTT(NTT(x)) != x"
     zs.zero_()
     prewarm(chains, mode, args.prewarm_ms)
-    R = region(chains, mode, args.steps, args.region_ms)
+    R = region(chains, mode, args.steps, exact=True)
     torch.cuda.synchronize(dev)
     assert torch.equal(zs, xs), "INTT(NTT(x)) != x after the timed region"
     elapsed, total_steps, launches, M, shader_mhz = R["elapsed"], R["steps"], R["replays"], R["M"], R["shader_mhz"]
     head = summary(R, mode)
     value = head["value"]
-    # the same steps with ONE launch in flight at a time (one stream, all 64 batches): what a single launch of the dominant kernel
-    # takes in a dense stream -- the figure a profiler can reproduce (rocprofv3 --kernel-trace serialises the dispatches of all
-    # streams: in its trace of this script no two launches overlap)
-    if S > 1:
-        prewarm([solo], mode, 20.0)
-        one = summary(region([solo], mode, args.steps, ROOFLINE_REGION_MS), mode)
-    else:
-        one = head
-
-    # ---- the chip's own clock: every workgroup of every launch stamps the 100 MHz reference counter at entry
-    # and exit (fz_diag_stamps_*); a launch = [min entry, max exit] over its workgroups.  Neither a kernel trace (it serialises
-    # the streams) nor HIP events (host-side markers) can show launches of different streams overlapping; these can.
-    def merged(iv):
-        out_ = []
-        for a_, b_ in sorted(iv):
-            if out_ and a_ <= out_[-1][1]:
-                out_[-1][1] = max(out_[-1][1], b_)
-            else:
-                out_.append([a_, b_])
-        return out_
-
-    def stamp_pass(cs, n_launch, rounds=3):
-        """n_launch full launches per chain (+ the opening and the closing one) captured WITH stamp slots, then `rounds` times:
-        reset, ONE replay of every chain's recording side by side, read.  -> the last round's table and all rounds' figures"""
-        graphs = []
-        for c_ in cs:
-            c_.ctx.diag_stamps_begin(n_launch + 2, (n_launch + 2) * 2 * D * B)     # (at most one workgroup per row)
-            c_.k = 0
-            c_.ctx.graph_begin()
-            rc_ = c_.run(n_launch * D, "pipe") | c_.end("pipe")
-            graphs.append(c_.ctx.graph_end())
-            c_.ctx.diag_stamps_stop()
-            assert rc_ == 0, f"capture failed: {lib.fz_last_error()}"
-        for g in graphs:
-            g.launch()                                       # (upload)
-        torch.cuda.synchronize(dev)
-        per_launch_bytes = 8 * d * B * 2 * D
-        rounds_out, table = [], []
-        for _ in range(rounds):
-            prewarm(cs, "pipe", 10.0)                        # steady clocks; these launches carry no slots
-            for c_ in cs:
-                c_.ctx.diag_stamps_reset()
-            torch.cuda.synchronize(dev)
-            for c_ in cs:
-                c_.ctx.timer_start()
-            for g in graphs:
-                g.launch()
-            ev = [c_.ctx.timer_stop_ms() for c_ in cs]
-            recs = [c_.ctx.diag_stamps_read(n_launch + 2) for c_ in cs]
-            t0_ = min(int(r_[0][r_[3] > 0].min()) for r_ in recs)
-            iv, full_d, gaps, table = [], [], [], []
-            for j, (st_, en_, ls_, wg_) in enumerate(recs):
-                assert len(st_) == n_launch + 1 and (wg_ > 0).all(), (len(st_), wg_.tolist())
-                st_u, en_u, ls_u = [(x_.astype(np.int64) - t0_) / 100.0 for x_ in (st_, en_, ls_)]     # ticks of 10 ns -> us
-                iv += list(zip(st_u.tolist(), en_u.tolist()))
-                full_d += (en_u - st_u)[1:-1].tolist()       # (the first launch is forward-only, the last inverse-only)
-                gaps += (st_u[1:] - en_u[:-1]).tolist()
-                table += [{"stream": j, "launch": k_, "start_us": round(float(st_u[k_]), 2), "end_us": round(float(en_u[k_]), 2),
-                           "last_workgroup_in_us": round(float(ls_u[k_]), 2), "workgroups": int(wg_[k_])} for k_ in range(len(st_u))]
-            span = max(b_ for _, b_ in iv) - min(a_ for a_, _ in iv)
-            busy = sum(b_ - a_ for a_, b_ in merged(iv))
-            total_b = per_launch_bytes * n_launch * len(cs)  # the two half launches of a chain = one full one: n_launch + 1 dispatches
-            rounds_out.append({"span_us": span, "busy_us": busy, "in_flight": sum(b_ - a_ for a_, b_ in iv) / busy,
-                               "frac": total_b / (span * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                               "launch_us": float(np.mean(full_d)), "launch_us_median": float(np.median(full_d)),
-                               "gap_us": float(np.mean(gaps)), "event_ms": ev, "frac_by_events": total_b / (max(ev) * 1e-3) / 1e9 / HBM_PEAK_GBS})
-        for g in graphs:
-            g.destroy()
-        best = sorted(rounds_out, key=lambda r_: r_["frac"])[len(rounds_out) // 2]      # the median round
-        return dict(best, rounds=rounds_out, launches_per_stream=n_launch + 1, streams=len(cs), bytes_per_launch=per_launch_bytes,
-                    table=table, clock="s_memrealtime (100 MHz reference counter, one for the chip), ticks of 10 ns",
-                    what="per launch: [min entry, max exit] over its workgroups' own stamps; span = first entry to last exit of the replay; "
-                         "in_flight = sum of launch durations / time at least one launch was running; frac = algorithmic bytes / span / 8 TB/s")
-
-    stamps_chip = stamps_one = None
-    if mode == "pipe" and not args.no_stamps:
-        try:
-            stamps_chip = stamp_pass(chains, 32)
-            stamps_one = stamp_pass([solo], 32) if S > 1 else stamps_chip
-            torch.cuda.synchronize(dev)
-            assert torch.equal(zs, xs), "INTT(NTT(x)) != x on the stamped passes"
-        except fusion_hip.FusionHipError as e:
-            stamps_chip = stamps_one = {"error": repr(e)}
-
-    # ---- context for the roofline figures (which come from the timed region itself, below): begin/end events bound to EVERY
-    # dispatch (hipExtLaunchKernelGGL) of instrumented passes on ONE stream over all 64 batches, launched one by one right after
-    # the timed region (a hipGraph cannot carry the events) -- the duration of a launch that starts on an idle memory system.
-    n_inst, n_pass = 200, 2
-    dom_kind = 0 if args.two_launch else 2              # the dominant launch: the forward kernel, or the multi-job launch
-    per_inst = 2 if args.two_launch else 1
-    dom_all, inv_all, passes = [], [], []
-    for _ in range(n_pass):
-        prewarm([solo], mode, 20.0)                      # dense launches first: a one-by-one pass leaves the device half idle
-        rc = solo.run(D, mode)                           # (the forward-only launch that opens the run: not instrumented)
-        ctx.profile_begin(per_inst * n_inst + 2, args.sample_every)
-        for _ in range(n_inst):
-            rc |= solo.run(D, mode)
-        assert rc == 0, f"launch failed: {lib.fz_last_error()}"
-        us, kind = ctx.profile_end_samples(per_inst * n_inst + 2)
-        rc = solo.end(mode)
-        assert rc == 0, f"launch failed: {lib.fz_last_error()}"
-        f_, i_ = us[kind == dom_kind], us[kind == 1]
-        assert len(f_) >= n_inst // args.sample_every - 1, (len(f_), len(us))
-        dom_all.append(f_)
-        inv_all.append(i_)
-        passes.append({"avg_us": float(f_.mean()), "median_us": float(np.median(f_)), "max_us": float(f_.max()), "count": int(len(f_)),
-                       "inverse_avg_us": float(i_.mean()) if len(i_) else None})
-    torch.cuda.synchronize(dev)
-    assert torch.equal(zs, xs), "INTT(NTT(x)) != x on the instrumented passes"
-    dom_all = np.concatenate(dom_all)
-    inv_all = np.concatenate(inv_all)
-    iso_us = float(dom_all.mean())
-    # SURVEY 8d: 8*d algorithmic bytes per transform; one dominant launch = D x 4096 forward + D x 4096 inverse transforms
-    units_per_launch = B if args.two_launch else 2 * D * B
-    dom_bytes = 8 * d * units_per_launch
-    # THE per-launch fraction (`roofline.frac`): algorithmic bytes per launch / the launch's average duration with ONE launch in
-    # flight -- HIP events on the kernel's stream around a dense single-stream region of the same steps / its launches.  This is
-    # the figure rocprofv3 --kernel-trace --stats reproduces (it serialises dispatches), profiles/ + DESIGN.md section 6.
-    # `roofline.chip`: the headline's timed region itself -- `streams` launches in flight on as many HIP streams; algorithmic bytes
-    # moved / the region's duration by HIP events on every stream = `value` x 2048 B: what the chip achieves on batches of 4096;
-    # `roofline.chip.device_clock`: the same from the kernels' own timestamps.
-    ach = one["frac"] * HBM_PEAK_GBS
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its LAST step (step K - 1: chain (K - 1) % S's last): the forward
+        # transforms of that step's batch and the inverse transforms of those, exact in float64
+        b_last = chains[(args.steps - 1) % S].last
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t_ in (("ntt_forward", ys[b_last]), ("ntt_inverse", zs[b_last])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t_.cpu().numpy().astype(np.float64))
     if args.two_launch:
-        kernel_name = "ntt_fwd4<8, true, 1, 8>"
         launch_text = "fz_ntt_forward + fz_ntt_inverse: two launches per step"
     else:
-        cus = props.multi_processor_count                  # the launcher's rule (fz_launch_ntt_multi): row groups per wave by the launch's rows
-        rows_ = 2 * D * B
-        nr_ = 1 if rows_ <= 24 * cus else (2 if rows_ <= 48 * cus else 4)
-        tab_ = 4 if 2 * D <= 4 else (8 if 2 * D <= 8 else 32)
-        if chain_ctx[0].diag_ntt_schedule(rows_) == 16:                # the library's own crossover (fz_diag_ntt_schedule)
-            kernel_name = f"ntt_jobs16<8, true, FzJobsN<{tab_}>>"
-        else:
-            kernel_name = f"ntt_jobs4<8, true, {nr_}, {(8 if rows_ >= 8 * cus else 4 if rows_ >= 4 * cus else 1) if nr_ == 1 else 2}, FzJobsN<{tab_}>>"
         launch_text = (f"software-pipelined over {D} batches: forward of batches i+1..i+{D} + inverse of batches i-{D - 1}..i in one "
                        f"fz_ntt_multi launch ({2 * D} jobs) per {D} steps")
-    traffic, traffic_src = pmc_traffic(kernel_name.split(", FzJobsN")[0], units_per_launch)      # prefix: whatever follows the launch shape
-
-    def stamp_brief(sp):
-        if not isinstance(sp, dict) or "frac" not in sp:
-            return sp
-        return {k_: sp[k_] for k_ in ("frac", "in_flight", "launch_us", "gap_us", "span_us", "frac_by_events", "launches_per_stream", "streams")}
-
     full = {
         "metric": METRIC, "value": value, "unit": "NTT/s", "n_gpus": world, "steps": args.steps, "repeats": launches * M,
         "warmup": args.warmup, "ms_per_step": elapsed / total_steps * 1e3, "higher_is_better": True,
@@ -1007,36 +898,177 @@ def main():
                    "streams": S, "step": launch_text,
                    "parallelism": f"{world} independent rank(s); per rank {S} HIP stream(s), each walking its own {NBATCH // S} of the {NBATCH} batches",
                    "arithmetic": "exact integers carried in fp64 lanes (bit-identical to the reference's int arithmetic); int32 in and out",
-                   "launch": ("one by one" if args.no_graph else f"{S} hipGraph(s) of {M}x{args.steps} steps together, {launches} replays") +
-                             f": timed region {elapsed * 1e3:.0f} ms (>= {args.region_ms:.0f} ms asked)",
+                   "launch": ("one by one" if args.no_graph else f"{S} chain(s) of hipGraphs (<= 1000 steps each), replayed once") +
+                             f": timed region {elapsed * 1e3:.1f} ms = the {total_steps} steps",
                    "prewarm_ms": args.prewarm_ms,
                    "host_threads_on": placement or "all allowed CPUs (no GPU-local NUMA node found, or FZ_NO_PIN=1)"},
         "ranks": ranks,
-        "roofline": {"bound": "hbm", "kernel": kernel_name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": one["frac"], "traffic": traffic, "traffic_source": traffic_src,
-                     "bytes_per_launch": dom_bytes, "units_per_launch": units_per_launch,
-                     "avg_launch_us": one["launch_us"], "in_flight": 1,
-                     "operands": f"cold: rotation of {NBATCH} batches",
-                     "timing": "HIP events around a dense one-stream region of the same steps / launches (one launch in flight)",
-                     "one_stream": one,
-                     "device_clock": stamp_brief(stamps_one),
-                     "chip": {"streams": S, "achieved": head["frac"] * HBM_PEAK_GBS, "frac": head["frac"], "unit": "GB/s",
-                              "launch_us_in_flight": head["launch_us"], "launch_interval_us": head["launch_interval_us"],
-                              "launches_timed": int(round(total_steps / per_launch_steps[mode])),
-                              "per_chain_event_ms": R["ev_ms"], "per_chain_steps": R["chain_steps"],
-                              "device_clock": stamp_brief(stamps_chip),
-                              "what": "the timed region of `value`: `streams` launches in flight, one per HIP stream; algorithmic bytes of "
-                                      "all launches / the region's duration by HIP events on every stream (the slowest chain's); device_clock: "
-                                      "the same quantity over a 33-launch replay per stream from the kernels' own entry / exit timestamps"},
-                     "isolated": {"avg_launch_us": iso_us, "median_launch_us": float(np.median(dom_all)),
-                                  "frac": dom_bytes / (iso_us * 1e-6) / 1e9 / HBM_PEAK_GBS, "launches": int(len(dom_all)),
-                                  "inverse_avg_launch_us": float(inv_all.mean()) if len(inv_all) else None, "passes": passes,
-                                  "what": f"begin/end events bound to EVERY dispatch (hipExtLaunchKernelGGL) of {n_pass} passes of {n_inst} "
-                                          "launches issued one by one from Python on ONE stream after the timed region: the host paces them, "
-                                          "so a launch may start on an idle memory system; context, not the fraction"},
-                     "shader_mhz": shader_mhz, "butterflies_per_s": value * (d // 2) * 8},
-        "device_timestamps": {"chip": stamps_chip, "one_stream": stamps_one},
     }
+    if args.full:
+        # the same steps with ONE launch in flight at a time (one stream, all 64 batches): what a single launch of the dominant kernel
+        # takes in a dense stream -- the figure a profiler can reproduce (rocprofv3 --kernel-trace serialises the dispatches of all
+        # streams: in its trace of this script no two launches overlap)
+        if S > 1:
+            prewarm([solo], mode, 20.0)
+            one = summary(region([solo], mode, args.steps, ROOFLINE_REGION_MS), mode)
+        else:
+            one = head
+
+        # ---- the chip's own clock: every workgroup of every launch stamps the 100 MHz reference counter at entry
+        # and exit (fz_diag_stamps_*); a launch = [min entry, max exit] over its workgroups.  Neither a kernel trace (it serialises
+        # the streams) nor HIP events (host-side markers) can show launches of different streams overlapping; these can.
+        def merged(iv):
+            out_ = []
+            for a_, b_ in sorted(iv):
+                if out_ and a_ <= out_[-1][1]:
+                    out_[-1][1] = max(out_[-1][1], b_)
+                else:
+                    out_.append([a_, b_])
+            return out_
+
+        def stamp_pass(cs, n_launch, rounds=3):
+            """n_launch full launches per chain (+ the opening and the closing one) captured WITH stamp slots, then `rounds` times:
+            reset, ONE replay of every chain's recording side by side, read.  -> the last round's table and all rounds' figures"""
+            graphs = []
+            for c_ in cs:
+                c_.ctx.diag_stamps_begin(n_launch + 2, (n_launch + 2) * 2 * D * B)     # (at most one workgroup per row)
+                c_.k = 0
+                c_.ctx.graph_begin()
+                rc_ = c_.run(n_launch * D, "pipe") | c_.end("pipe")
+                graphs.append(c_.ctx.graph_end())
+                c_.ctx.diag_stamps_stop()
+                assert rc_ == 0, f"capture failed: {lib.fz_last_error()}"
+            for g in graphs:
+                g.launch()                                       # (upload)
+            torch.cuda.synchronize(dev)
+            per_launch_bytes = 8 * d * B * 2 * D
+            rounds_out, table = [], []
+            for _ in range(rounds):
+                prewarm(cs, "pipe", 10.0)                        # steady clocks; these launches carry no slots
+                for c_ in cs:
+                    c_.ctx.diag_stamps_reset()
+                torch.cuda.synchronize(dev)
+                for c_ in cs:
+                    c_.ctx.timer_start()
+                for g in graphs:
+                    g.launch()
+                ev = [c_.ctx.timer_stop_ms() for c_ in cs]
+                recs = [c_.ctx.diag_stamps_read(n_launch + 2) for c_ in cs]
+                t0_ = min(int(r_[0][r_[3] > 0].min()) for r_ in recs)
+                iv, full_d, gaps, table = [], [], [], []
+                for j, (st_, en_, ls_, wg_) in enumerate(recs):
+                    assert len(st_) == n_launch + 1 and (wg_ > 0).all(), (len(st_), wg_.tolist())
+                    st_u, en_u, ls_u = [(x_.astype(np.int64) - t0_) / 100.0 for x_ in (st_, en_, ls_)]     # ticks of 10 ns -> us
+                    iv += list(zip(st_u.tolist(), en_u.tolist()))
+                    full_d += (en_u - st_u)[1:-1].tolist()       # (the first launch is forward-only, the last inverse-only)
+                    gaps += (st_u[1:] - en_u[:-1]).tolist()
+                    table += [{"stream": j, "launch": k_, "start_us": round(float(st_u[k_]), 2), "end_us": round(float(en_u[k_]), 2),
+                               "last_workgroup_in_us": round(float(ls_u[k_]), 2), "workgroups": int(wg_[k_])} for k_ in range(len(st_u))]
+                span = max(b_ for _, b_ in iv) - min(a_ for a_, _ in iv)
+                busy = sum(b_ - a_ for a_, b_ in merged(iv))
+                total_b = per_launch_bytes * n_launch * len(cs)  # the two half launches of a chain = one full one: n_launch + 1 dispatches
+                rounds_out.append({"span_us": span, "busy_us": busy, "in_flight": sum(b_ - a_ for a_, b_ in iv) / busy,
+                                   "frac": total_b / (span * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                                   "launch_us": float(np.mean(full_d)), "launch_us_median": float(np.median(full_d)),
+                                   "gap_us": float(np.mean(gaps)), "event_ms": ev, "frac_by_events": total_b / (max(ev) * 1e-3) / 1e9 / HBM_PEAK_GBS})
+            for g in graphs:
+                g.destroy()
+            best = sorted(rounds_out, key=lambda r_: r_["frac"])[len(rounds_out) // 2]      # the median round
+            return dict(best, rounds=rounds_out, launches_per_stream=n_launch + 1, streams=len(cs), bytes_per_launch=per_launch_bytes,
+                        table=table, clock="s_memrealtime (100 MHz reference counter, one for the chip), ticks of 10 ns",
+                        what="per launch: [min entry, max exit] over its workgroups' own stamps; span = first entry to last exit of the replay; "
+                             "in_flight = sum of launch durations / time at least one launch was running; frac = algorithmic bytes / span / 8 TB/s")
+
+        stamps_chip = stamps_one = None
+        if mode == "pipe" and not args.no_stamps:
+            try:
+                stamps_chip = stamp_pass(chains, 32)
+                stamps_one = stamp_pass([solo], 32) if S > 1 else stamps_chip
+                torch.cuda.synchronize(dev)
+                assert torch.equal(zs, xs), "INTT(NTT(x)) != x on the stamped passes"
+            except fusion_hip.FusionHipError as e:
+                stamps_chip = stamps_one = {"error": repr(e)}
+
+        # ---- context for the roofline figures (which come from the timed region itself, below): begin/end events bound to EVERY
+        # dispatch (hipExtLaunchKernelGGL) of instrumented passes on ONE stream over all 64 batches, launched one by one right after
+        # the timed region (a hipGraph cannot carry the events) -- the duration of a launch that starts on an idle memory system.
+        n_inst, n_pass = 200, 2
+        dom_kind = 0 if args.two_launch else 2              # the dominant launch: the forward kernel, or the multi-job launch
+        per_inst = 2 if args.two_launch else 1
+        dom_all, inv_all, passes = [], [], []
+        for _ in range(n_pass):
+            prewarm([solo], mode, 20.0)                      # dense launches first: a one-by-one pass leaves the device half idle
+            rc = solo.run(D, mode)                           # (the forward-only launch that opens the run: not instrumented)
+            ctx.profile_begin(per_inst * n_inst + 2, args.sample_every)
+            for _ in range(n_inst):
+                rc |= solo.run(D, mode)
+            assert rc == 0, f"launch failed: {lib.fz_last_error()}"
+            us, kind = ctx.profile_end_samples(per_inst * n_inst + 2)
+            rc = solo.end(mode)
+            assert rc == 0, f"launch failed: {lib.fz_last_error()}"
+            f_, i_ = us[kind == dom_kind], us[kind == 1]
+            assert len(f_) >= n_inst // args.sample_every - 1, (len(f_), len(us))
+            dom_all.append(f_)
+            inv_all.append(i_)
+            passes.append({"avg_us": float(f_.mean()), "median_us": float(np.median(f_)), "max_us": float(f_.max()), "count": int(len(f_)),
+                           "inverse_avg_us": float(i_.mean()) if len(i_) else None})
+        torch.cuda.synchronize(dev)
+        assert torch.equal(zs, xs), "INTT(NTT(x)) != x on the instrumented passes"
+        dom_all = np.concatenate(dom_all)
+        inv_all = np.concatenate(inv_all)
+        iso_us = float(dom_all.mean())
+        # SURVEY 8d: 8*d algorithmic bytes per transform; one dominant launch = D x 4096 forward + D x 4096 inverse transforms
+        units_per_launch = B if args.two_launch else 2 * D * B
+        dom_bytes = 8 * d * units_per_launch
+        # THE per-launch fraction (`roofline.frac`): algorithmic bytes per launch / the launch's average duration with ONE launch in
+        # flight -- HIP events on the kernel's stream around a dense single-stream region of the same steps / its launches.  This is
+        # the figure rocprofv3 --kernel-trace --stats reproduces (it serialises dispatches), profiles/ + DESIGN.md section 6.
+        # `roofline.chip`: the headline's timed region itself -- `streams` launches in flight on as many HIP streams; algorithmic bytes
+        # moved / the region's duration by HIP events on every stream = `value` x 2048 B: what the chip achieves on batches of 4096;
+        # `roofline.chip.device_clock`: the same from the kernels' own timestamps.
+        ach = one["frac"] * HBM_PEAK_GBS
+        if args.two_launch:
+            kernel_name = "ntt_fwd4<8, true, 1, 8>"
+        else:
+            cus = props.multi_processor_count                  # the launcher's rule (fz_launch_ntt_multi): row groups per wave by the launch's rows
+            rows_ = 2 * D * B
+            nr_ = 1 if rows_ <= 24 * cus else (2 if rows_ <= 48 * cus else 4)
+            tab_ = 4 if 2 * D <= 4 else (8 if 2 * D <= 8 else 32)
+            if chain_ctx[0].diag_ntt_schedule(rows_) == 16:                # the library's own crossover (fz_diag_ntt_schedule)
+                kernel_name = f"ntt_jobs16<8, true, FzJobsN<{tab_}>>"
+            else:
+                kernel_name = f"ntt_jobs4<8, true, {nr_}, {(8 if rows_ >= 8 * cus else 4 if rows_ >= 4 * cus else 1) if nr_ == 1 else 2}, FzJobsN<{tab_}>>"
+        traffic, traffic_src = pmc_traffic(kernel_name.split(", FzJobsN")[0], units_per_launch)      # prefix: whatever follows the launch shape
+
+        def stamp_brief(sp):
+            if not isinstance(sp, dict) or "frac" not in sp:
+                return sp
+            return {k_: sp[k_] for k_ in ("frac", "in_flight", "launch_us", "gap_us", "span_us", "frac_by_events", "launches_per_stream", "streams")}
+
+        full["roofline"] = {"bound": "hbm", "kernel": kernel_name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": one["frac"], "traffic": traffic, "traffic_source": traffic_src,
+                            "bytes_per_launch": dom_bytes, "units_per_launch": units_per_launch,
+                            "avg_launch_us": one["launch_us"], "in_flight": 1,
+                            "operands": f"cold: rotation of {NBATCH} batches",
+                            "timing": "HIP events around a dense one-stream region of the same steps / launches (one launch in flight)",
+                            "one_stream": one,
+                            "device_clock": stamp_brief(stamps_one),
+                            "chip": {"streams": S, "achieved": head["frac"] * HBM_PEAK_GBS, "frac": head["frac"], "unit": "GB/s",
+                                     "launch_us_in_flight": head["launch_us"], "launch_interval_us": head["launch_interval_us"],
+                                     "launches_timed": int(round(total_steps / per_launch_steps[mode])),
+                                     "per_chain_event_ms": R["ev_ms"], "per_chain_steps": R["chain_steps"],
+                                     "device_clock": stamp_brief(stamps_chip),
+                                     "what": "the timed region of `value`: `streams` launches in flight, one per HIP stream; algorithmic bytes of "
+                                             "all launches / the region's duration by HIP events on every stream (the slowest chain's); device_clock: "
+                                             "the same quantity over a 33-launch replay per stream from the kernels' own entry / exit timestamps"},
+                            "isolated": {"avg_launch_us": iso_us, "median_launch_us": float(np.median(dom_all)),
+                                         "frac": dom_bytes / (iso_us * 1e-6) / 1e9 / HBM_PEAK_GBS, "launches": int(len(dom_all)),
+                                         "inverse_avg_launch_us": float(inv_all.mean()) if len(inv_all) else None, "passes": passes,
+                                         "what": f"begin/end events bound to EVERY dispatch (hipExtLaunchKernelGGL) of {n_pass} passes of {n_inst} "
+                                                 "launches issued one by one from Python on ONE stream after the timed region: the host paces them, "
+                                                 "so a launch may start on an idle memory system; context, not the fraction"},
+                            "shader_mhz": shader_mhz, "butterflies_per_s": value * (d // 2) * 8}
+        full["device_timestamps"] = {"chip": stamps_chip, "one_stream": stamps_one}
 
     # ---- everything below is a side leg: the headline is measured.  A watchdog prints the line with whatever is there if
     # a leg hangs (a collective that never completes cannot be cancelled from Python) ------------------------------------
@@ -1046,7 +1078,8 @@ def main():
     def emit(watchdog=None):
         if watchdog:
             full["watchdog"] = watchdog
-        full["full"] = write_full(args.full_out, full)
+        if args.full:
+            full["full"] = write_full(args.full_out, full)
         text = compact_line(full)
         print(text)
         sys.stdout.flush()
@@ -1091,7 +1124,7 @@ def main():
         timed_on_stream=timed_on_stream, exchange_ctx=exchange_ctx, comm=comm, collective=collective, backend=backend, shard_range=shard_range,
         allreduce_sum_i64=allreduce_sum_i64, HBM_PEAK_GBS=HBM_PEAK_GBS, MIN_REGION_MS=MIN_REGION_MS, SECPAR=SECPAR)
 
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         # the single-stream forms over the same batches: one launch in flight at a time
         def solo_leg(mode_, what):
             prewarm([solo], mode_, 20.0)
@@ -1119,7 +1152,7 @@ def main():
         # the host by construction (fusion.py:632-652) -- the line carries both so that neither is read for the other.
         if not args.no_end_to_end:
             full["end_to_end"] = leg("end_to_end", lambda: L.end_to_end(env))
-        if args.full:
+        if not args.no_extra_legs:
             for name in L.FULL_LEGS:
                 if name != "end_to_end" or args.no_end_to_end:
                     full[name] = leg(name, lambda: getattr(L, name)(env))
@@ -1133,7 +1166,7 @@ def main():
     stage[0] = "cpu_baseline"
     done.set()                                          # the bounded CPU sample is not under the watchdog
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not args.headline_only:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.headline_only:
             cb = cpu_baseline(args.cpu_seconds)
             full["cpu_baseline"] = cb
             sch = cb.get("scheme") or {}

@@ -17,6 +17,8 @@ Files
   scheme_128.npz / scheme_256.npz / scheme.json
                 end-to-end setup/keygen/sign/aggregate/verify with every intermediate array [G6]
   kat.json      compact replay data extracted from the reference's own reproducible KAT CSVs  [G7]
+  reference_tests.json
+                the names of the reference's test functions, per test file, in file order (tests/test_reference_case_map.py)
 """
 import csv
 import hashlib
@@ -569,8 +571,21 @@ def gen_kat():
     print("kat.json written:", {k: len(v) for k, v in out.items() if isinstance(v, list)})
 
 
+def gen_reference_tests():
+    """the names only (`def test_...(` at the start of a line), per file of the reference's tests/, in file order"""
+    out = {}
+    for name in sorted(os.listdir(os.path.join(REF, "tests"))):
+        if name.startswith("test_") and name.endswith(".py"):
+            with open(os.path.join(REF, "tests", name)) as fh:
+                out["tests/" + name] = re.findall(r"^def (test_\w+)\(", fh.read(), flags=re.M)
+    with open(os.path.join(HERE, "reference_tests.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("reference_tests.json written:", {k: len(v) for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["algebra", "bulk", "scheme", "kat", "many", "kat_flow"]
+    which = sys.argv[1:] or ["algebra", "bulk", "scheme", "kat", "many", "kat_flow", "reference_tests"]
     if "full" in sys.argv[1:]:                  # ~5 minutes on 8 cores: only on request
         gen_scheme_full()
     if "full128" in sys.argv[1:]:               # secpar 128 AT ITS CAPACITY (1796 signers, fusion.py:24)
@@ -591,3 +606,5 @@ if __name__ == "__main__":
         gen_scheme()
     if "kat" in which:
         gen_kat()
+    if "reference_tests" in which:
+        gen_reference_tests()

@@ -461,7 +461,7 @@ def test_bench_headline_keeps_its_streams_with_rccl_in_the_process():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--headline-only", "--single-rank-comm", "--full-out", os.devnull],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--headline-only", "--single-rank-comm", "--full-out", os.devnull],
                        capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1]
@@ -472,6 +472,31 @@ def test_bench_headline_keeps_its_streams_with_rccl_in_the_process():
     # by the chip's own clock: the two chains' launches really ran side by side (queue-sharing chains run one after the other)
     assert dev["in_flight"] > 1.5, f"{dev}: the chains share a hardware queue"
     assert chip > 1.05 * one, f"two streams reach {chip:.3f} of the peak against {one:.3f} on one"
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(coracle, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes what the
+    last of them computed.  K = 37 steps on 2 chains: step 36 is chain 0's 19th, whose batch is rotation index 18 (seed
+    20261003 + 18 000): the inverse output is that batch, the forward output its transforms by the oracle."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    full_out, dump = tmp_path / "full.json", tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "37", "--warmup", "3",
+                        "--dump-outputs", str(dump), "--full-out", str(full_out)], capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+    assert d["steps"] == 37 and d["warmup"] == 3 and d["unit"] == "NTT/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and "the 37 steps" in d["config"]["launch"] and d["config"]["streams"] == 2
+    assert d["roofline"] == {} and d["cpu_baseline"] is None and "sign_verify" not in d and "full" not in d
+    assert not full_out.exists()
+    fwd, inv = np.load(dump / "ntt_forward.npy"), np.load(dump / "ntt_inverse.npy")
+    assert fwd.dtype == inv.dtype == np.float64 and fwd.shape == inv.shape == (4096, 256)
+    P = O.PARAMS[256]
+    x = O.splitmix_centered(20261003 + 18 * 1000, 4096 * 256).reshape(4096, 256)
+    assert np.array_equal(inv, x.astype(np.float64))
+    assert np.array_equal(fwd, coracle.ntt_forward(x, P["q"], P["root"]).astype(np.float64))
 
 
 def test_bench_sign_verify_leg_with_the_exchange_on_its_second_stream():
@@ -486,7 +511,7 @@ def test_bench_sign_verify_leg_with_the_exchange_on_its_second_stream():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     vals = {}
     for name, extra in (("plain", []), ("exchange", ["--single-rank-comm", "--exchange-standin-us", "20"])):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--full-out", os.devnull] + extra,
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-extra-legs", "--no-cpu-baseline", "--full-out", os.devnull] + extra,
                            capture_output=True, text=True, timeout=400, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])

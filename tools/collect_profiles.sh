@@ -78,16 +78,16 @@ step timeout -k 10 600 python bench.py --full --full-out $OUT/${TAG}_bench_full.
 python3 tools/stamp_table.py $OUT/${TAG}_bench_full.json > $OUT/${TAG}_device_timestamps.txt
 cd /tmp && export TMPDIR=/tmp
 # per-kernel durations from the profiler: the bench's transform launches, the cold kernel table, the challenge pipeline
-step timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --headline-only --streams 1 --full-out $OUT/prof_bench_full.json > $OUT/prof.log 2>&1
+step timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --headline-only --streams 1 --full-out $OUT/prof_bench_full.json > $OUT/prof.log 2>&1
 cp $OUT/prof/*/*_kernel_stats.csv $OUT/${TAG}_bench_rocprofv3_kernel_stats.csv 2>/dev/null
 # the line bench.py printed IN THAT PROFILED RUN: its roofline.avg_launch_us and the kernel_stats average above are the same
 # launches measured two ways
 grep -a '^{"metric"' $OUT/prof.log | tail -1 > $OUT/${TAG}_bench_under_rocprofv3_line.json
-step timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof2 -- python3 $R/bench.py --headline-only --full-out $OUT/prof2_bench_full.json > $OUT/prof2.log 2>&1
+step timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof2 -- python3 $R/bench.py --full --headline-only --full-out $OUT/prof2_bench_full.json > $OUT/prof2.log 2>&1
 cp $OUT/prof2/*/*_kernel_stats.csv $OUT/${TAG}_bench_2streams_rocprofv3_kernel_stats.csv 2>/dev/null
 grep -a '^{"metric"' $OUT/prof2.log | tail -1 > $OUT/${TAG}_bench_2streams_under_rocprofv3_line.json
 # ... and the whole default run (the scheme legs' kernels as the bench runs them)
-step timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profd -- python3 $R/bench.py --no-cpu-baseline --full-out /dev/null > $OUT/profd.log 2>&1
+step timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profd -- python3 $R/bench.py --full --no-extra-legs --no-cpu-baseline --full-out /dev/null > $OUT/profd.log 2>&1
 cp $OUT/profd/*/*_kernel_stats.csv $OUT/${TAG}_bench_default_rocprofv3_kernel_stats.csv 2>/dev/null
 step timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profk -- python3 $R/tools/kernel_table.py > $OUT/profk.log 2>&1
 cp $OUT/profk/*/*_kernel_stats.csv $OUT/${TAG}_kernel_table_rocprofv3_kernel_stats.csv 2>/dev/null
@@ -96,7 +96,7 @@ cp $OUT/profc/*/*_kernel_stats.csv $OUT/${TAG}_challenge_rocprofv3_kernel_stats.
 # PMC passes: one counter set per pass, nothing else traced
 for set in FETCH_SIZE WRITE_SIZE "GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU"; do
   n=$(echo $set | tr " " "_" | cut -c1-30)
-  step timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/pmcb/$n -- python3 $R/bench.py --headline-only --streams 1 --no-stamps --no-graph --steps 50 --prewarm-ms 20 --full-out $OUT/pmcb_bench_full.json > $OUT/pmcb_$n.log 2>&1
+  step timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/pmcb/$n -- python3 $R/bench.py --full --headline-only --streams 1 --no-stamps --no-graph --steps 50 --prewarm-ms 20 --full-out $OUT/pmcb_bench_full.json > $OUT/pmcb_$n.log 2>&1
   step timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/pmc20/$n -- python3 $R/tools/probes/prof_ntt.py 20 30 > $OUT/pmc20_$n.log 2>&1
   step timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/pmcs/$n -- python3 $R/tools/probes/prof_scheme.py 12 $OUT/pmcs_manifest.json > $OUT/pmcs_$n.log 2>&1
 done

@@ -14,7 +14,7 @@ for s, q in ((1, None), (2, None), (3, None), (4, None), (4, "4"), (4, "16"), (6
     env.pop("GPU_MAX_HW_QUEUES", None)
     if q is not None:
         env["GPU_MAX_HW_QUEUES"] = q
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--headline-only", "--streams", str(s), "--full-out", "/dev/null"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--headline-only", "--streams", str(s), "--full-out", "/dev/null"],
                        env=env, capture_output=True, text=True, timeout=300)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     if r.returncode != 0 or not line:
