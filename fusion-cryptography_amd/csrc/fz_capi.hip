@@ -1225,6 +1225,18 @@ int fz_verify_with_target_batch_async(fz_ctx *ctx, const int32_t *d_A, const int
     return fz_launch_verify_fused(ctx, d_A, d_sig, d_target, groups, l, beta_vf, omega_vf, d_verdicts);
 }
 
+int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const int32_t *d_vk,
+                               const int32_t *d_c_hat, size_t N, int l, int64_t beta, int64_t omega, int *d_verdicts) {
+    FZ_REQUIRE(ctx && l >= 1 && beta >= 0 && omega >= 0, "bad argument");
+    if (N == 0) return FZ_OK;
+    FZ_REQUIRE(d_A && d_sig && d_vk && d_c_hat && d_verdicts, "NULL argument");
+    FZ_REQUIRE((((uintptr_t)d_A | (uintptr_t)d_sig) & 15) == 0, "A and the signatures must be 16-byte aligned");
+    if (ctx->logd != 6 && ctx->logd != 8)
+        return fz_set_error(FZ_E_UNSUPPORTED, "per-signature verification needs the fused kernel (degree 64 or 256)");
+    FZ_DEV(ctx);
+    return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
+}
+
 int fz_verify_partials_batch_async(fz_ctx *ctx, const int32_t *d_A, const int64_t *d_partial, size_t partial_stride,
                                    const int64_t *d_target_partial, size_t target_stride, size_t groups, int l,
                                    int64_t beta_vf, int64_t omega_vf, int *d_verdicts) {

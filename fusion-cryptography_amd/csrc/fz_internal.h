@@ -203,6 +203,8 @@ int fz_launch_verify_fused_i64(fz_ctx *ctx, const int32_t *A, const int64_t *sig
                                size_t target_stride, size_t groups, int l, int64_t beta, int64_t omega, int *d_verdict);
 int fz_launch_verify_fused(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *target, size_t groups, int l,
                            int64_t beta, int64_t omega, int *d_verdict);
+int fz_launch_verify_signatures(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *vk, const int32_t *c, size_t N,
+                                int l, int64_t beta, int64_t omega, int *d_verdict);
 
 // launchers (fz_pointwise.hip)
 enum { FZ_OP_MUL = 0, FZ_OP_ADD = 1, FZ_OP_SUB = 2, FZ_OP_NEG = 3, FZ_OP_MULACC = 4 };

@@ -1220,12 +1220,20 @@ __device__ __forceinline__ int centred_any(int64_t v, const FzMod &m) { return (
 // test needs no centring at all -- the inverse transform's outputs r satisfy |r| <= q/2 + q * 2^-13; if |r| <= beta then r is
 // already the centred residue and passes; if |r| > beta then |cent(r)| >= q - |r| >= q/2 - q * 2^-13 > beta (or cent(r) = r):
 // max |r| > beta <=> max |cent(r)| > beta.  Likewise r == 0 (mod q) <=> r == 0, since |r| < q.  Saves 8 of ~180 ops per row.
+//
+// Target from the key (vk != nullptr, uniform; per-signature verification, fz_verify_signatures_async): the comparison's
+// target is not read from `target` but formed here, cent(vkL (.) c + vkR), from the key rows [groups][2][D] and the
+// challenges [groups][D] -- the one-time scheme's own equation, i.e. a single signer with alpha_hat == 1.  The three words a
+// comparing thread needs are requested at kernel entry, so their latency hides under the row loop.  A run-time argument
+// and not a template parameter: the 32 instantiations stay what tests/test_isa_checks.py pins, and both compare sites of
+// the new form are in them.  Any int32 key and challenge: |vkL * c| < 2^62 (fz_mulmod), |. + vkR| < 2^32 (fz_cent).
 template <int LOGD, bool FAST, typename T, bool ORDERED, bool IMAD>
 __global__ __launch_bounds__(64 * kVerifyWaves) void verify_fused(const int32_t *A, const T *sig,
                                                                   size_t sig_stride,
                                                                   const T *target, size_t target_stride, int l, long long beta,
                                                                   long long omega, int lazy, const double2 *__restrict__ itw2,
-                                                                  FzTwA twA, FzMod m, double *part, int *state, int *verdict) {
+                                                                  FzTwA twA, FzMod m, double *part, int *state, int *verdict,
+                                                                  const int32_t *vk, const int32_t *chal) {
     constexpr int NR = 1;                 // one row group per wave iteration (two: 248.5 against 243.9 us per 8192 aggregates, round 3)
     using TW = double2;
     constexpr int D = 1 << LOGD, LP = D / 4, PPW = 64 / LP;
@@ -1242,6 +1250,10 @@ __global__ __launch_bounds__(64 * kVerifyWaves) void verify_fused(const int32_t 
     target += (size_t)g * target_stride;
     part += (size_t)g * D;                          // [groups][D] exact fp64 sums of `observed`, zero between launches
     state += g;                                     // arrivals (bits 0-15), norm failures (16-23), weight failures (24-31)
+    const bool keyed = vk != nullptr;
+    __shared__ int s_tgt[D];                        // keyed: the target, formed before the row loop
+    // the value a comparing thread (threadIdx.x < D) compares with, centred (s_tgt: written by this same thread)
+    auto want = [&]() -> int { return keyed ? s_tgt[threadIdx.x] : centred_any(target[threadIdx.x], m); };
 
     TW twl[LOGD / 2 - 1][3];
     inv4_load_twiddles<LOGD, TW>(twl, itw2, mm);
@@ -1270,6 +1282,14 @@ __global__ __launch_bounds__(64 * kVerifyWaves) void verify_fused(const int32_t 
     long long ihi[4] = {0, 0, 0, 0}, ilo[4] = {0, 0, 0, 0};      // IMAD: exact integer sums of sigma * hi and sigma * lo
     int task = r * kVerifyWaves + wave;
     if (task < tasks) fetch(task);
+    // keyed: the key and challenge words are requested right behind the first row, so the two latencies overlap (the row
+    // loop waits for that row anyway); the target goes to LDS, not into a register held across the loop -- the other
+    // forms' register count, hence occupancy, is what it was
+    if (keyed && threadIdx.x < D) {
+        const int32_t kL = vk[(size_t)g * 2 * D + threadIdx.x], kR = vk[(size_t)g * 2 * D + D + threadIdx.x];
+        const int32_t kc = chal[(size_t)g * D + threadIdx.x];
+        s_tgt[threadIdx.x] = (int)fz_cent(fz_mulmod((double)kL, (double)kc, m) + (double)kR, m);
+    }
     for (; task < tasks; task += NR * step) {
         double a[NR][4];
 #pragma unroll
@@ -1334,7 +1354,7 @@ __global__ __launch_bounds__(64 * kVerifyWaves) void verify_fused(const int32_t 
             for (int w = 0; w < kVerifyWaves; ++w)
 #pragma unroll
                 for (int q = 0; q < PPW; ++q) sum += accbuf[w * 256 + q * D + threadIdx.x];
-            if ((int)fz_cent_wide(sum, m) != centred_any(target[threadIdx.x], m)) atomicOr(&s_flags, 1);
+            if ((int)fz_cent_wide(sum, m) != want()) atomicOr(&s_flags, 1);
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -1378,7 +1398,7 @@ __global__ __launch_bounds__(64 * kVerifyWaves) void verify_fused(const int32_t 
     if (!s_last) return;
     if (threadIdx.x < D) {                          // read and re-arm in one operation
         const double sum = __hip_atomic_exchange(part + threadIdx.x, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)fz_cent_wide(sum, m) != centred_any(target[threadIdx.x], m)) atomicOr(&s_flags, 1);   // both centred
+        if ((int)fz_cent_wide(sum, m) != want()) atomicOr(&s_flags, 1);   // both centred
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1627,7 +1647,8 @@ int fz_launch_keygen_fused(fz_ctx *ctx, const int32_t *A, const int32_t *coef, i
 
 template <typename T>
 static int launch_verify_fused(fz_ctx *ctx, const int32_t *A, const T *sig, size_t sig_stride, const T *target,
-                               size_t target_stride, size_t groups, int l, int64_t beta, int64_t omega, int *d_verdict) {
+                               size_t target_stride, size_t groups, int l, int64_t beta, int64_t omega, int *d_verdict,
+                               const int32_t *vk = nullptr, const int32_t *chal = nullptr) {
     if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "fused verify: degree 64 or 256 only");
     // about one row per wave while that leaves the chip under-filled (measured: one aggregate 22 us with one workgroup,
     // 4.5 us with 21; 64 aggregates 9.2 us with 4-8 workgroups each, 14.6 us with 22)
@@ -1650,7 +1671,7 @@ static int launch_verify_fused(fz_ctx *ctx, const int32_t *A, const T *sig, size
     const dim3 grid((unsigned)R, (unsigned)groups), block(64 * kVerifyWaves);
 #define FZ_VF3(LOGD, FAST, ORD, IM) hipLaunchKernelGGL((verify_fused<LOGD, FAST, T, ORD, IM>), grid, block, 0, ctx->stream, A, sig, sig_stride, target, \
                                                    target_stride, l, (long long)beta, (long long)omega, lazy, (const double2 *)ctx->d_itw2, \
-                                                   ctx->itwA, ctx->mod, part, state, d_verdict)
+                                                   ctx->itwA, ctx->mod, part, state, d_verdict, vk, chal)
     // integer accumulation of A * sigma pays its once-per-wave conversion back only over several rows per wave (measured: 1.18 M
     // vector instructions against 1.10 M per launch when the l rows are spread one per wave over 21 workgroups)
     // ... and it is exact for at most 2^15 products per lane (fz_arith.h): a longer sum takes the fp64 form
@@ -1671,6 +1692,25 @@ int fz_launch_verify_fused(fz_ctx *ctx, const int32_t *A, const int32_t *sig, co
                            int64_t beta, int64_t omega, int *d_verdict) {
     return launch_verify_fused<int32_t>(ctx, A, sig, (size_t)l * ctx->degree, target, (size_t)ctx->degree, groups, l, beta, omega,
                                         d_verdict);
+}
+
+// per-signature verification: signer g's target formed in the kernel from its key row vk [g][2][D] and challenge c [g][D]
+// (verify_fused, "target from the key").  One launch per at most max-grid-y signers (blockIdx.y is the signer); the chunks
+// share the verification scratch, which every launch re-arms, so they simply follow each other on the stream.
+int fz_launch_verify_signatures(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *vk, const int32_t *c, size_t N,
+                                int l, int64_t beta, int64_t omega, int *d_verdict) {
+    int ymax = 0;
+    int rc = fz_check_hip(hipDeviceGetAttribute(&ymax, hipDeviceAttributeMaxGridDimY, ctx->device), "max grid y");
+    if (rc != FZ_OK) return rc;
+    if (ymax < 1) return fz_set_error(FZ_E_HIP, "max grid y reported as %d", ymax);
+    const size_t D = (size_t)ctx->degree, sig_stride = (size_t)l * D;
+    for (size_t g0 = 0; g0 < N; g0 += (size_t)ymax) {
+        const size_t n = N - g0 < (size_t)ymax ? N - g0 : (size_t)ymax;
+        rc = launch_verify_fused<int32_t>(ctx, A, sig + g0 * sig_stride, sig_stride, nullptr, 0, n, l, beta, omega, d_verdict + g0,
+                                          vk + g0 * 2 * D, c + g0 * D);
+        if (rc != FZ_OK) return rc;
+    }
+    return FZ_OK;
 }
 
 // the aggregates and targets as int64 partial sums (e.g. straight after the all-reduce), group g at base + g * stride

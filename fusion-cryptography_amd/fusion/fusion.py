@@ -525,6 +525,31 @@ def verify(params: Params, keys: List[OneTimeVerificationKey], messages: List[st
     return (code == 0), VERDICT_REASONS[code]
 
 
+def verify_signatures(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
+                      signatures: List[Signature]) -> List[Tuple[bool, str]]:
+    """NOT in the reference (an extension of the object face): is each single signature valid?  -> one (ok, reason) per signer,
+    reasons from fusion_hip.SIGNATURE_REASONS.  Signer i passes when A . sigma_i == vkL_i * c_i + vkR_i (c_i = hash_ch(vk_i,
+    m_i)), ||INTT(sigma_i)||_inf <= VF_BD_INTERMEDIATE_{secpar} (the bound of ONE honest signature) and every row's weight
+    <= omega_vf -- verify() of a one-signer aggregate with alpha == 1, but against the single-signature bound.  Screen
+    untrusted contributions with it before aggregate(): one bad signature makes the aggregate fail verify() without saying
+    whose it was.  Batched exactly as fusion_hip.scheme.BatchScheme.verify_signatures (one challenge pass, one launch).
+    Unequal numbers of keys, messages and signatures raise fusion_hip.FusionHipError(FZ_E_BADARG)."""
+    from fusion_hip import FusionHipError, SIGNATURE_REASONS
+    from fusion_hip._lib import FZ_E_BADARG
+    from fusion_hip.scheme import BatchScheme, signature_from_object, vk_from_object
+    if not (len(keys) == len(messages) == len(signatures)):
+        raise FusionHipError(FZ_E_BADARG, f"{len(keys)} keys, {len(messages)} messages, {len(signatures)} signatures")
+    n, d, l = len(keys), params.degree, params.num_rows_sk
+    vk = np.stack([vk_from_object(params, k) for k in keys]) if n else np.zeros((0, 2, d), dtype=np.int32)
+    sig = np.stack([signature_from_object(params, s) for s in signatures]) if n else np.zeros((0, l, d), dtype=np.int32)
+    bs = BatchScheme(params)
+    try:
+        codes = bs.verify_signatures(vk, list(messages), sig)
+    finally:
+        bs.close()
+    return [(int(c) == 0, SIGNATURE_REASONS[int(c)]) for c in codes]
+
+
 _ORIGINALS.update({name: globals()[name] for name in (
     "decode_bytes_to_polynomial_coefficients", "hash_ch", "parse_challenge", "transform", "sample_coefficient_matrix", "hash_ag",
     "sample_polynomial_coefficient_representation")})

@@ -28,6 +28,15 @@ VERDICT_REASONS = {
     5: "Weight of aggregate signature too large.",
 }
 
+# per-signature verification (BatchScheme.verify_signatures, fz_verify_signatures_async; not a reference function): the codes
+# it can return, in the order it checks them
+SIGNATURE_REASONS = {
+    0: "",
+    3: "Target doesn't match image of signature.",
+    4: "Norm of signature too large.",
+    5: "Weight of signature too large.",
+}
+
 
 def _as_i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
@@ -368,6 +377,12 @@ class Context:
         check(self._lib, self._lib.fz_verify_with_target_batch_async(self._h, c_void_p(d_A), c_void_p(d_sig),
                                                                      c_void_p(d_target), groups, l, beta_vf,
                                                                      omega_vf, c_void_p(d_verdicts)))
+
+    def verify_signatures_async_dev(self, d_A, d_sig, d_vk, d_c, N, l, beta, omega, d_verdicts):
+        """per-signature verification: signer i against cent(vkL_i (.) c_i + vkR_i), norm <= beta, weight <= omega; codes
+        (0, 3, 4, 5) to d_verdicts [N] (asynchronous).  d_vk [N][2][d] as keygen writes it, d_c [N][d]."""
+        check(self._lib, self._lib.fz_verify_signatures_async(self._h, c_void_p(d_A), c_void_p(d_sig), c_void_p(d_vk),
+                                                              c_void_p(d_c), N, l, beta, omega, c_void_p(d_verdicts)))
 
     def reduce_i64_dev(self, d_in, d_out, count):
         check(self._lib, self._lib.fz_reduce_i64(self._h, c_void_p(d_in), c_void_p(d_out), count))

@@ -10,8 +10,56 @@ sig [N][l][d], aggregate [l][d]; all int32, centred.
 import numpy as np
 
 from . import hostpipe
-from ._lib import FZ_E_UNSUPPORTED, FusionHipError
-from .context import Context, DeviceArray, VERDICT_REASONS, get_context
+from ._lib import FZ_E_BADARG, FZ_E_UNSUPPORTED, FusionHipError
+from .context import Context, DeviceArray, SIGNATURE_REASONS, VERDICT_REASONS, get_context  # noqa: F401 (SIGNATURE_REASONS: re-exported)
+
+# The bound of ONE honest signature, ||INTT(sigma)||_inf <= beta_sk * (1 + min(degree, omega_ch) * CH_BD): the reference's
+# VF_BD_INTERMEDIATE_128 / _256 (fusion.py:59-64; fusion/fusion.py keeps them under the same names), which it only uses to
+# build beta_vf.  A table and not a formula over the params: CH_BD_128 = 3 is not the live beta_ch (1).
+_SIGNATURE_BOUNDS = {128: 4264, 256: 3172}
+
+
+def signature_bound(params):
+    """the infinity-norm bound of a single signature for params.secpar (4264 at 128, 3172 at 256); no device needed.  Any
+    other parameter set has no such constant: FusionHipError(FZ_E_BADARG), pass `beta` explicitly instead."""
+    secpar = getattr(params, "secpar", None)
+    if secpar not in _SIGNATURE_BOUNDS:
+        raise FusionHipError(FZ_E_BADARG, f"no single-signature bound for secpar {secpar!r}: pass beta explicitly")
+    return _SIGNATURE_BOUNDS[secpar]
+
+
+def screened_alpha_coefficients(P, L, R, pre, c_hat, valid=None, threads=None, order=None):
+    """hash_ag without the transforms (fusion.py:632-652) for ONE aggregate of the signers with valid[i] set: sort them by
+    str(vk) (fusion.py:661-663, :693), the one serial SHAKE-256 over the sorted list, decode.
+    P: the fz_scheme_params of hostpipe.scheme_params; L, R [N][d] key rows, pre [N][32] prehashes, c_hat [N][d], all in the
+    callers' order; valid: [N] booleans, None = all.  order: sort_by_vk_string of ALL N keys when the caller has it (the sort
+    is stable, so the valid signers' order is that order filtered).
+    -> (order: caller indices of the valid signers in sorted order, alpha [N][d] coefficient rows in the callers' order, ZERO
+    rows for the rest).  The aggregate and the target are sums over signers: with zero coefficients they are sums over the
+    valid ones, so nothing has to be compacted or permuted on the device.  No device needed."""
+    L = hostpipe._rows(L, P.degree)
+    R = hostpipe._rows(R, P.degree)
+    n = L.shape[0]
+    alpha = np.zeros((n, P.degree), dtype=np.int32)
+    if valid is None:
+        keep = None
+    else:
+        keep = np.asarray(valid, dtype=bool).reshape(n)
+        if keep.all():
+            keep = None
+    if order is None:
+        if keep is None:
+            order = hostpipe.sort_by_vk_string(P, L, R, threads)
+        else:
+            idx = np.flatnonzero(keep)
+            order = idx[hostpipe.sort_by_vk_string(P, L[idx], R[idx], threads)] if idx.size else idx
+    elif keep is not None:
+        order = np.asarray(order)[keep[order]]
+    if order.size:
+        pre = np.ascontiguousarray(pre, dtype=np.uint8).reshape(-1, 32)
+        c_hat = hostpipe._rows(c_hat, P.degree)
+        alpha[order] = hostpipe.aggregation_coefficients(P, L[order], R[order], pre[order], c_hat[order], threads)
+    return order, alpha
 
 
 class BatchScheme:
@@ -252,13 +300,7 @@ class BatchScheme:
         """hash_ag without the transforms (fusion.py:632-652) for ONE aggregate: sort by str(vk) (fusion.py:661-663, :693), the
         one serial SHAKE-256 over the sorted list, decode; -> (order, alpha coefficient rows scattered back to the CALLERS'
         order).  The aggregate and the target are sums over signers, so nothing else ever has to be permuted."""
-        threads = threads or self.threads
-        if order is None:
-            order = hostpipe.sort_by_vk_string(self.P, L, R, threads)
-        alpha_sorted = hostpipe.aggregation_coefficients(self.P, L[order], R[order], pre[order], c_hat[order], threads)
-        alpha = np.empty_like(alpha_sorted)
-        alpha[order] = alpha_sorted
-        return order, alpha
+        return screened_alpha_coefficients(self.P, L, R, pre, c_hat, None, threads or self.threads, order)
 
     def hash_ag_dev(self, vk, messages):
         """Everything aggregate() and verify() derive from the keys and messages, device-resident and in the callers' order:
@@ -323,6 +365,94 @@ class BatchScheme:
                 b.free()
             if own:
                 dS.free()
+
+    # ---- one signature at a time (not in the reference) ----------------------------------------------------
+    def _screen(self, vk, messages, sig, beta, omega, want_hash_ag):
+        """the per-signature verdicts of N signers, -> (codes [N] int32, dC, c_hat host copy, prehash), the last two None unless
+        want_hash_ag.  One challenge pass, one launch, one verdict download; vk is uploaded once (the challenge pipeline reads
+        the same copy)."""
+        n = vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+        if n != len(messages):
+            raise FusionHipError(FZ_E_BADARG, f"{n} keys but {len(messages)} messages")
+        beta = signature_bound(self.params) if beta is None else int(beta)
+        omega = int(self.params.omega_vf) if omega is None else int(omega)
+        if beta < 0 or omega < 0:
+            raise FusionHipError(FZ_E_BADARG, f"bounds must be non-negative (beta={beta}, omega={omega})")
+        for a, shape in ((vk, (n, 2, self.d)), (sig, (n, self.l, self.d))):
+            if isinstance(a, DeviceArray) and (a.shape != shape or a.dtype != np.int32):
+                raise FusionHipError(FZ_E_BADARG, f"device array {a.shape} {a.dtype}: {shape} int32 expected")
+        if n == 0:
+            return np.zeros(0, dtype=np.int32), None, None, None
+        dK, own_k = self._dev(vk, (n, 2, self.d))
+        dC = dS = dV = None
+        own_s = False
+        try:
+            if self.device_hash:
+                try:
+                    dC, pre = self.challenges_dev(dK, messages, want_prehash=want_hash_ag)
+                    c_hat = dC.numpy() if want_hash_ag else None
+                except FusionHipError as e:
+                    if e.code != FZ_E_UNSUPPORTED:
+                        raise
+                    self.device_hash = False
+            if dC is None:                                   # the host pipeline: parameter sets the device one does not cover
+                c_hat, pre = self.challenges(dK, messages)
+                dC = DeviceArray.from_numpy(self.ctx, c_hat)
+            dS, own_s = self._dev(sig, (n, self.l, self.d))
+            dV = DeviceArray(self.ctx, (n,))
+            self.ctx.verify_signatures_async_dev(self._A_dev().ptr, dS.ptr, dK.ptr, dC.ptr, n, self.l, beta, omega, dV.ptr)
+            codes = dV.numpy()
+        except Exception:
+            if dC is not None:
+                dC.free()
+            raise
+        finally:
+            for b, own in ((dK, own_k), (dS, own_s), (dV, True)):
+                if b is not None and own:
+                    b.free()
+        if not want_hash_ag:
+            dC.free()
+            return codes, None, None, None
+        return codes, dC, c_hat, pre
+
+    def verify_signatures(self, vk, messages, sig, beta=None, omega=None):
+        """Per-signature verification (not a reference function): -> int32 codes [N], 0 where signer i's signature is valid
+        for (vk[i], messages[i]), else the first failing check (SIGNATURE_REASONS): 3 when A (.) sig_i != vkL_i (.) c_i + vkR_i,
+        4 when ||INTT(sig_i)||_inf > beta, 5 when a row's weight > omega.  That is verify() of the aggregate of one signer with
+        alpha_hat == 1, against the bound of ONE signature: beta defaults to signature_bound(params) (4264 at secpar 128,
+        3172 at 256; a params object of another secpar must pass it), omega to params.omega_vf.  vk [N][2][d] and sig
+        [N][l][d] may be numpy arrays or DeviceArrays (keygen_batch(..., keep_vk=True) / sign_batch(..., device=True)).
+        Unequal numbers of keys and messages raise FusionHipError(FZ_E_BADARG): a caller error, not a verdict."""
+        return self._screen(vk, messages, sig, beta, omega, False)[0]
+
+    def aggregate_screened(self, vk, messages, sig):
+        """aggregate() over the signers whose signature passes verify_signatures, for aggregators that take untrusted
+        contributions: -> (aggregate [l][d] or None when no signer passes, codes [N]).  The aggregate is bit for bit
+        aggregate(vk[ok], messages[ok], sig[ok]) -- one bad contribution no longer spoils the aggregate, and the codes say
+        whose it was.  One challenge pass serves both steps; hash_ag runs over the valid signers only, its coefficients are
+        scattered back with zero rows for the rejected ones, so the signature rows are never compacted."""
+        codes, dC, c_hat, pre = self._screen(vk, messages, sig, None, None, True)
+        if dC is None:
+            return None, codes
+        dAl = dO = dS = None
+        own = False
+        try:
+            valid = codes == 0
+            if not valid.any():
+                return None, codes
+            _, L, R = self._split_vk(vk)
+            _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads)
+            n = alpha.shape[0]
+            dAl = DeviceArray.from_numpy(self.ctx, alpha)
+            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
+            dS, own = self._dev(sig, (n, self.l, self.d))
+            dO = DeviceArray(self.ctx, (self.l, self.d))
+            self.ctx.aggregate_core_dev(dS.ptr, dAl.ptr, dO.ptr, n, self.l)
+            return dO.numpy(), codes
+        finally:
+            for b, o in ((dC, True), (dAl, True), (dO, True), (dS, own)):
+                if b is not None and o:
+                    b.free()
 
     # ---- many aggregates at once ------------------------------------------------------------------------
     def _hash_ag_many(self, vk, messages, sizes):

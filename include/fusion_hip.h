@@ -316,6 +316,13 @@ FZ_API int fz_verify_with_target_batch_async(fz_ctx *ctx, const int32_t *d_A, co
                                              const int32_t *d_target, size_t groups, int l,
                                              int64_t beta_vf, int64_t omega_vf, int *d_verdicts);
 
+/* per-signature verification (not a reference function): signer i passes when A (.) sig_i == vkL_i (.) c_i + vkR_i and
+ * ||INTT(sig_i)||_inf <= beta, weight <= omega.  d_sig [N][l][degree], d_vk [N][2][degree] as fz_keygen_core writes it,
+ * d_c_hat [N][degree]; FZ_VERDICT_* codes (0, 3, 4, 5) to d_verdicts [N] on the context's stream.  Degree 64 or 256.
+ * d_A and d_sig 16-byte aligned; N == 0 does nothing. */
+FZ_API int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const int32_t *d_vk,
+                                      const int32_t *d_c_hat, size_t N, int l, int64_t beta, int64_t omega, int *d_verdicts);
+
 /* ---- the exchange step across GPUs: RCCL all-reduce of the int64 partial sums -------------------
  * aggregate() (fusion.py:670-676) and verify()'s target (:706-714) are sums over signers; with the signers sharded over
  * GPUs each rank holds exact int64 partials (fz_aggregate_partial*, fz_target_partial*, fz_aggregate_target_partial_batch)
