@@ -848,8 +848,9 @@ __global__ __launch_bounds__(64) void norm_weight_kernel(const int32_t *coef, si
             long long x = coef[row * (size_t)degree + j];
             long long ax = x < 0 ? -x : x;
             mx = ax > mx ? ax : mx;
-            // |x| <= 2^31 < 2q, so x mod q == 0 iff x in {0, q, -q}
-            w += (ax != 0 && ax != (long long)q) ? 1 : 0;
+            // x mod q == 0 iff |x| mod q == 0; |x| <= 2^31 fits a uint32, so one exact 32-bit remainder serves every odd
+            // q < 2^32 (an unreduced multiple such as 2q or -3q of a small modulus counts as zero, as in the reference)
+            w += ((uint32_t)ax % q != 0u) ? 1 : 0;
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
