@@ -1237,6 +1237,40 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
 }
 
+// compact byte encoding: the checks both directions share; *w = bit_length(2 * bound)
+static int records_args(fz_ctx *ctx, const void *src, const void *dst, size_t n, int rows, int64_t bound, const int *d_status, int *w) {
+    FZ_REQUIRE(ctx && rows >= 1, "bad argument");
+    FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "bound %lld outside [1, (q-1)/2]", (long long)bound);
+    if (n == 0) return FZ_OK;
+    FZ_REQUIRE(src && dst && d_status, "NULL argument");
+    FZ_REQUIRE((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)d_status) & 15) == 0, "rows, bytes and status must be 16-byte aligned");
+    if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
+    FZ_REQUIRE((uint64_t)rows * (uint64_t)ctx->degree <= 0x7fffffffull && n <= ((size_t)-1 >> 3) / ((size_t)rows * ctx->degree),
+               "%zu records of %d rows are too many", n, rows);
+    int b = 0;
+    while ((2 * bound) >> b) ++b;
+    *w = b;
+    return FZ_OK;
+}
+
+int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n, int rows, int coef, int64_t bound, uint8_t *d_bytes,
+                            int *d_status) {
+    int w = 0;
+    FZ_TRY(records_args(ctx, d_rows, d_bytes, n, rows, bound, d_status, &w));
+    if (n == 0) return FZ_OK;
+    FZ_DEV(ctx);
+    return fz_launch_records(ctx, false, d_rows, d_bytes, n, rows, coef != 0, w, bound, d_status);
+}
+
+int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int coef, int64_t bound, int32_t *d_rows,
+                            int *d_status) {
+    int w = 0;
+    FZ_TRY(records_args(ctx, d_bytes, d_rows, n, rows, bound, d_status, &w));
+    if (n == 0) return FZ_OK;
+    FZ_DEV(ctx);
+    return fz_launch_records(ctx, true, d_bytes, d_rows, n, rows, coef != 0, w, bound, d_status);
+}
+
 int fz_verify_partials_batch_async(fz_ctx *ctx, const int32_t *d_A, const int64_t *d_partial, size_t partial_stride,
                                    const int64_t *d_target_partial, size_t target_stride, size_t groups, int l,
                                    int64_t beta_vf, int64_t omega_vf, int *d_verdicts) {

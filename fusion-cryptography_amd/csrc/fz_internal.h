@@ -57,6 +57,7 @@ struct fz_ctx {
     int grid_fwd, grid_inv;      // resident-grid caps for the persistent NTT kernels
     int grid_pm;                 // resident grid of the fused product kernel (0 = not queried yet)
     int grid_pm16;               // ... of its 16-per-lane form
+    int grid_rec[4];             // ... of the byte-encoding kernels: [encode, decode] x [coefficient kinds, keys] (degree 64 / 256)
     int knob_ntt_rows;           // FZ_NTT_ROWS = 1 | 2 | 4: row groups per wave of the radix-4 kernels (0 = by batch size)
     // per-dispatch timing of the NTT kernels (fz_profile_begin/end): event pairs bound to the
     // dispatch itself via hipExtLaunchKernelGGL, i.e. kernel begin -> kernel end on its own stream
@@ -205,6 +206,10 @@ int fz_launch_verify_fused(fz_ctx *ctx, const int32_t *A, const int32_t *sig, co
                            int64_t beta, int64_t omega, int *d_verdict);
 int fz_launch_verify_signatures(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *vk, const int32_t *c, size_t N,
                                 int l, int64_t beta, int64_t omega, int *d_verdict);
+// compact byte encoding (degree 64 / 256): n records of rows * degree values, w-bit fields u = z + bound; encode (decode = false)
+// rows -> bytes, decode bytes -> rows; d_status [n] cleared, then 0 or FZ_VERDICT_NORM / FZ_VERDICT_ENCODING; failed records zeroed
+int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
+                      int *d_status);
 
 // launchers (fz_pointwise.hip)
 enum { FZ_OP_MUL = 0, FZ_OP_ADD = 1, FZ_OP_SUB = 2, FZ_OP_NEG = 3, FZ_OP_MULACC = 4 };

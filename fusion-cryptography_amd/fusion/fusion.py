@@ -550,6 +550,46 @@ def verify_signatures(params: Params, keys: List[OneTimeVerificationKey], messag
     return [(int(c) == 0, SIGNATURE_REASONS[int(c)]) for c in codes]
 
 
+def to_bytes(params: Params, obj, aggregate: bool = False) -> bytes:
+    """NOT in the reference (an extension of the object face): the canonical compact bytes of a OneTimeVerificationKey or a
+    Signature; aggregate=True encodes a Signature under the aggregate bound beta_vf instead of the
+    single-signature one.  Raises ValueError with the reason when the object cannot be encoded (its norm is over the bound)."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import BatchScheme, signature_from_object, vk_from_object
+    if isinstance(obj, OneTimeVerificationKey):
+        kind, rows = "vk", vk_from_object(params, obj)[None]
+    elif isinstance(obj, Signature):
+        kind, rows = ("aggregate" if aggregate else "signature"), signature_from_object(params, obj)[None]
+    else:
+        raise TypeError(f"to_bytes takes a OneTimeVerificationKey or a Signature, not {type(obj).__name__}")
+    bs = BatchScheme(params)
+    try:
+        data, codes = bs.encode(kind, rows)
+    finally:
+        bs.close()
+    if codes[0]:
+        raise ValueError(ENCODING_REASONS[int(codes[0])])
+    return data.tobytes()
+
+
+def from_bytes(params: Params, kind: str, data: bytes):
+    """NOT in the reference: the inverse of to_bytes for one record of `kind` ("vk", "signature" or "aggregate") -> a
+    OneTimeVerificationKey or a Signature.  Raises ValueError for a wrong length or a record that is not canonical."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import BatchScheme, encoded_size, signature_to_object, vk_to_object
+    size = encoded_size(params, kind)
+    if len(data) != size:
+        raise ValueError(f"a {kind!r} record is {size} bytes, not {len(data)}")
+    bs = BatchScheme(params)
+    try:
+        rows, codes = bs.decode(kind, data)
+    finally:
+        bs.close()
+    if codes[0]:
+        raise ValueError(ENCODING_REASONS[int(codes[0])])
+    return vk_to_object(params, rows[0]) if kind == "vk" else signature_to_object(params, rows[0])
+
+
 _ORIGINALS.update({name: globals()[name] for name in (
     "decode_bytes_to_polynomial_coefficients", "hash_ch", "parse_challenge", "transform", "sample_coefficient_matrix", "hash_ag",
     "sample_polynomial_coefficient_representation")})

@@ -37,6 +37,14 @@ SIGNATURE_REASONS = {
     5: "Weight of signature too large.",
 }
 
+# compact byte encoding (BatchScheme.encode / decode, fz_encode_records_async / fz_decode_records_async; not in the reference): the
+# per-record codes
+ENCODING_REASONS = {
+    0: "",
+    4: "Norm too large to encode.",
+    6: "Encoding is not canonical.",
+}
+
 
 def _as_i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
@@ -383,6 +391,17 @@ class Context:
         (0, 3, 4, 5) to d_verdicts [N] (asynchronous).  d_vk [N][2][d] as keygen writes it, d_c [N][d]."""
         check(self._lib, self._lib.fz_verify_signatures_async(self._h, c_void_p(d_A), c_void_p(d_sig), c_void_p(d_vk),
                                                               c_void_p(d_c), N, l, beta, omega, c_void_p(d_verdicts)))
+
+    def encode_records_async_dev(self, d_rows, n, rows, coef, bound, d_bytes, d_status):
+        """compact byte encoding of n records of `rows` rows: coef -> cent(INTT(row)), else the values
+        mod q, centred; codes (0, 4) to d_status [n], a refused record's bytes zero (asynchronous)"""
+        check(self._lib, self._lib.fz_encode_records_async(self._h, c_void_p(d_rows), n, rows, 1 if coef else 0, bound,
+                                                           c_void_p(d_bytes), c_void_p(d_status)))
+
+    def decode_records_async_dev(self, d_bytes, n, rows, coef, bound, d_rows, d_status):
+        """... and back: codes (0, 6) to d_status [n], a refused record's rows zero (asynchronous)"""
+        check(self._lib, self._lib.fz_decode_records_async(self._h, c_void_p(d_bytes), n, rows, 1 if coef else 0, bound,
+                                                           c_void_p(d_rows), c_void_p(d_status)))
 
     def reduce_i64_dev(self, d_in, d_out, count):
         check(self._lib, self._lib.fz_reduce_i64(self._h, c_void_p(d_in), c_void_p(d_out), count))

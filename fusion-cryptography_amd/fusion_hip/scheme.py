@@ -11,7 +11,8 @@ import numpy as np
 
 from . import hostpipe
 from ._lib import FZ_E_BADARG, FZ_E_UNSUPPORTED, FusionHipError
-from .context import Context, DeviceArray, SIGNATURE_REASONS, VERDICT_REASONS, get_context  # noqa: F401 (SIGNATURE_REASONS: re-exported)
+from .context import (Context, DeviceArray, ENCODING_REASONS, SIGNATURE_REASONS, VERDICT_REASONS,  # noqa: F401 (re-exported)
+                      get_context)
 
 # The bound of ONE honest signature, ||INTT(sigma)||_inf <= beta_sk * (1 + min(degree, omega_ch) * CH_BD): the reference's
 # VF_BD_INTERMEDIATE_128 / _256 (fusion.py:59-64; fusion/fusion.py keeps them under the same names), which it only uses to
@@ -26,6 +27,29 @@ def signature_bound(params):
     if secpar not in _SIGNATURE_BOUNDS:
         raise FusionHipError(FZ_E_BADARG, f"no single-signature bound for secpar {secpar!r}: pass beta explicitly")
     return _SIGNATURE_BOUNDS[secpar]
+
+
+# the kinds of the compact byte encoding: params -> (rows of a record, coefficient domain?, bound B)
+_ENCODING_KINDS = {
+    "vk": lambda p: (2, False, (p.modulus - 1) // 2),
+    "signature": lambda p: (p.num_rows_sk, True, signature_bound(p)),
+    "aggregate": lambda p: (p.num_rows_sk, True, int(p.beta_vf)),
+}
+
+
+def _encoding(params, kind):
+    """-> (rows, coef, bound, w, record_bytes) of `kind` for params; FusionHipError(FZ_E_BADARG) for an unknown kind or secpar"""
+    if kind not in _ENCODING_KINDS:
+        raise FusionHipError(FZ_E_BADARG, f"unknown encoding kind {kind!r}: one of {sorted(_ENCODING_KINDS)}")
+    signature_bound(params)                                    # the secpar check: only the reference's two parameter sets
+    rows, coef, bound = _ENCODING_KINDS[kind](params)
+    w = (2 * bound).bit_length()
+    return rows, coef, bound, w, rows * params.degree * w // 8
+
+
+def encoded_size(params, kind):
+    """bytes of one record of `kind` ("vk", "signature" or "aggregate") in the compact byte encoding; no device needed"""
+    return _encoding(params, kind)[4]
 
 
 def screened_alpha_coefficients(P, L, R, pre, c_hat, valid=None, threads=None, order=None):
@@ -452,6 +476,72 @@ class BatchScheme:
         finally:
             for b, o in ((dC, True), (dAl, True), (dO, True), (dS, own)):
                 if b is not None and o:
+                    b.free()
+
+    # ---- compact byte encoding (not in the reference) ------------------------------------
+    def encode(self, kind, rows):
+        """-> (data uint8 [N][encoded_size(params, kind)], codes int32 [N]): the canonical bytes of N keys ("vk", rows
+        [N][2][d]), signatures or aggregates ("signature" / "aggregate", rows [N][l][d]; one [l][d] aggregate is N = 1), as
+        numpy arrays or a DeviceArray.  codes[i] is 4 (ENCODING_REASONS) when record i is over its kind's bound -- exactly the
+        signatures verify_signatures rejects for the norm, the aggregates verify() rejects for it; keys never are -- and its
+        bytes are then zero."""
+        nrows, coef, bound, w, rb = _encoding(self.params, kind)
+        shape = rows.shape if isinstance(rows, DeviceArray) else np.shape(rows)
+        if kind != "vk" and len(shape) == 2:
+            shape = (1,) + tuple(shape)
+        if len(shape) != 3 or tuple(shape[1:]) != (nrows, self.d):
+            raise FusionHipError(FZ_E_BADARG, f"rows of shape {tuple(shape)}: [N][{nrows}][{self.d}] expected for {kind!r}")
+        if isinstance(rows, DeviceArray) and rows.dtype != np.int32:
+            raise FusionHipError(FZ_E_BADARG, f"device array of {rows.dtype}: int32 expected")
+        n = int(shape[0])
+        if n == 0:
+            return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
+        dR, own = self._dev(rows, (n, nrows, self.d))
+        dB, dV = DeviceArray(self.ctx, (n, rb), np.uint8), DeviceArray(self.ctx, (n,))
+        try:
+            self.ctx.encode_records_async_dev(dR.ptr, n, nrows, coef, bound, dB.ptr, dV.ptr)
+            return dB.numpy(), dV.numpy()
+        finally:
+            for b, o in ((dR, own), (dB, True), (dV, True)):
+                if o:
+                    b.free()
+
+    def decode(self, kind, data, device=False):
+        """-> (rows, codes int32 [N]): the records of `data` (bytes, bytearray, memoryview, a uint8 numpy array or a uint8
+        DeviceArray; N * encoded_size(params, kind) bytes) as int32 rows [N][2][d] ("vk") or [N][l][d], NTT domain, centred
+        -- numpy, or a DeviceArray with device=True (straight into verify_signatures / aggregate).  codes[i] is 6
+        (ENCODING_REASONS) when record i is not canonical (a field above 2B), and its rows are then zero.  A length that is not
+        a whole number of records raises FusionHipError(FZ_E_BADARG)."""
+        nrows, coef, bound, w, rb = _encoding(self.params, kind)
+        if isinstance(data, DeviceArray):
+            if data.dtype != np.uint8:
+                raise FusionHipError(FZ_E_BADARG, f"device array of {data.dtype}: uint8 expected")
+            nbytes = int(np.prod(data.shape))
+        else:
+            data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(data)
+            if data.dtype != np.uint8:
+                raise FusionHipError(FZ_E_BADARG, f"array of {data.dtype}: uint8 expected")
+            nbytes = data.size
+        if nbytes % rb:
+            raise FusionHipError(FZ_E_BADARG, f"{nbytes} bytes are not a whole number of {rb}-byte {kind!r} records")
+        n = nbytes // rb
+        if n == 0:
+            empty = np.zeros((0, nrows, self.d), dtype=np.int32)
+            return (DeviceArray.from_numpy(self.ctx, empty) if device else empty), np.zeros(0, dtype=np.int32)
+        own = not isinstance(data, DeviceArray)
+        dB = DeviceArray.from_numpy(self.ctx, data.reshape(n, rb)) if own else data
+        dR, dV = DeviceArray(self.ctx, (n, nrows, self.d)), DeviceArray(self.ctx, (n,))
+        try:
+            self.ctx.decode_records_async_dev(dB.ptr, n, nrows, coef, bound, dR.ptr, dV.ptr)
+            codes = dV.numpy()
+            if device:
+                out, dR = dR, None
+                return out, codes
+            return dR.numpy(), codes
+        finally:
+            for b, o in ((dB, own), (dR, True), (dV, True)):
+                if o and b is not None:
                     b.free()
 
     # ---- many aggregates at once ------------------------------------------------------------------------

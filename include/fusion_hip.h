@@ -54,6 +54,7 @@ extern "C" {
 #define FZ_VERDICT_TARGET_MISMATCH 3  /* "Target doesn't match image of aggregate signature." :721 */
 #define FZ_VERDICT_NORM            4  /* "Norm of aggregate signature too large."      :725      */
 #define FZ_VERDICT_WEIGHT          5  /* "Weight of aggregate signature too large."    :727      */
+#define FZ_VERDICT_ENCODING        6  /* "Encoding is not canonical." (fz_decode_records_async; not in the reference) */
 
 typedef struct fz_ctx fz_ctx;
 
@@ -322,6 +323,17 @@ FZ_API int fz_verify_with_target_batch_async(fz_ctx *ctx, const int32_t *d_A, co
  * d_A and d_sig 16-byte aligned; N == 0 does nothing. */
 FZ_API int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const int32_t *d_vk,
                                       const int32_t *d_c_hat, size_t N, int l, int64_t beta, int64_t omega, int *d_verdicts);
+
+/* compact byte encoding (not in the reference) -- the format: INTEGRATION.md section G.  n records of `rows` rows of
+ * `degree` values; coef != 0: a record holds cent(INTT(row)) (signatures, aggregates), coef == 0: the values mod q, centred
+ * (verification keys).  w = bit_length(2 * bound); record = rows * degree * w / 8 bytes.  Status per record to d_status [n]:
+ * encode 0 or FZ_VERDICT_NORM (some |z| > bound; the record's bytes are zero), decode 0 or FZ_VERDICT_ENCODING (some field
+ * > 2 * bound; the record's rows are zero).  Asynchronous on the context's stream; degree 64 or 256; 1 <= bound <= (q-1)/2;
+ * all pointers 16-byte aligned; n == 0 does nothing. */
+FZ_API int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n, int rows, int coef, int64_t bound,
+                                   uint8_t *d_bytes, int *d_status);
+FZ_API int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int coef, int64_t bound,
+                                   int32_t *d_rows, int *d_status);
 
 /* ---- the exchange step across GPUs: RCCL all-reduce of the int64 partial sums -------------------
  * aggregate() (fusion.py:670-676) and verify()'s target (:706-714) are sums over signers; with the signers sharded over
