@@ -353,6 +353,7 @@ static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint
         c->knob_no_imad = knob("FZ_NO_IMAD");
         c->knob_matvec_slices = knob("FZ_MATVEC_SLICES");
         c->knob_verify_cent = knob("FZ_VERIFY_CENT");
+        c->knob_multi_order = getenv("FZ_MULTI_ORDER") ? knob("FZ_MULTI_ORDER") : 1;
         // fz_malloc's block pool: FZ_POOL_MB megabytes at most over all contexts of the process (default 4096, 0 = every fz_free is a hipFree)
         c->pool_cap = (size_t)(getenv("FZ_POOL_MB") ? (knob("FZ_POOL_MB") < 0 ? 0 : knob("FZ_POOL_MB")) : 4096) << 20;
     }
@@ -1572,6 +1573,37 @@ int fz_diag_ntt_schedule(fz_ctx *ctx, size_t rows, int *family) {
     if (!radix4_exists || ctx->force_kernel == 16) *family = 16;
     else if (ctx->force_kernel == 4) *family = 4;
     else *family = rows >= (size_t)ctx->small_batch_rows ? 16 : 4;
+    return FZ_OK;
+}
+
+int fz_diag_multi_order(const fz_ntt_job *h_jobs, size_t n_jobs, const fz_ntt_job *h_prev, size_t n_prev, int degree,
+                        unsigned resident_workgroups, int ordered, int *h_order, uint32_t *h_end, int *out_consumers, int *out_keep) {
+    FZ_REQUIRE((n_jobs == 0 || (h_jobs && h_order && h_end)) && (n_prev == 0 || h_prev), "NULL argument");
+    FZ_REQUIRE(n_jobs <= (size_t)kFzMultiMax && n_prev <= (size_t)kFzMultiMax, "at most %d jobs per launch", kFzMultiMax);
+    FZ_REQUIRE(degree >= 32 && degree <= 256 && (degree & (degree - 1)) == 0 && resident_workgroups >= 1, "degree 32 .. 256, at least one workgroup");
+    FzMultiJobs J;
+    memset(&J, 0, sizeof(J));
+    FzProduced prev[kFzMultiMax];
+    for (size_t j = 0; j < n_jobs; ++j) {
+        FZ_REQUIRE(h_jobs[j].rows > 0 && h_jobs[j].rows < ((size_t)1 << 31), "job %zu: rows", j);
+        J.in[j] = h_jobs[j].d_in; J.out[j] = h_jobs[j].d_out;
+        J.rows[j] = (unsigned)h_jobs[j].rows | (h_jobs[j].inverse ? 0x80000000u : 0u);
+    }
+    J.n = (int)n_jobs;
+    for (size_t k = 0; k < n_prev; ++k) prev[k] = FzProduced{h_prev[k].d_out, (unsigned)h_prev[k].rows};
+    int consumers = 0, keep = 0;
+    (void)fz_multi_plan(J, degree, prev, (int)n_prev, ordered != 0, resident_workgroups, h_order, h_end, &consumers, &keep);
+    if (out_consumers) *out_consumers = consumers;
+    if (out_keep) *out_keep = keep;
+    return FZ_OK;
+}
+
+int fz_diag_multi_last(fz_ctx *ctx, int *h_order, size_t cap, size_t *n, int *out_consumers, int *out_keep) {
+    FZ_REQUIRE(ctx && n && (cap == 0 || h_order), "NULL argument");
+    *n = (size_t)ctx->last_n;
+    for (size_t k = 0; k < cap && k < (size_t)ctx->last_n; ++k) h_order[k] = ctx->last_order[k];
+    if (out_consumers) *out_consumers = ctx->last_consumers;
+    if (out_keep) *out_keep = ctx->last_keep;
     return FZ_OK;
 }
 

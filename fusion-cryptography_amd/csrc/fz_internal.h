@@ -31,6 +31,15 @@ static inline FzTw4 fz_tw4(const FzTwA &a) {
     return t;
 }
 
+// most jobs of one fz_ntt_multi launch (the table travels in the kernarg segment: FzMultiJobs below)
+constexpr int kFzMultiMax = 32;
+
+// what one multi-job launch wrote, in the order its jobs ran: the next launch of the context runs the jobs that read these first
+struct FzProduced {
+    const int32_t *out;
+    unsigned rows;
+};
+
 struct fz_ctx {
     int device;
     int num_cu;
@@ -97,6 +106,12 @@ struct fz_ctx {
     int knob_matvec_slices;      // FZ_MATVEC_SLICES = 1 | 2 | 4: k-range slices per column of the integer matvec kernel (0 = by batch size, -1 = the fp64 kernel)
     int knob_no_imad;            // FZ_NO_IMAD=1: A (.) y through the general fp64 multiply instead of integer multiply-adds (A/B runs)
     int knob_verify_cent;        // FZ_VERIFY_CENT=1: centre the inverse transform's outputs before the norm test even when beta allows skipping it
+    int knob_multi_order;        // FZ_MULTI_ORDER=0: a multi-job launch runs its jobs in table order, streaming stores throughout (1, the default: fz_multi_plan)
+    // the previous multi-job launch's outputs in the order they were produced (host memory, written when a launch is issued or
+    // CAPTURED: a graph replays the order it was captured with)
+    FzProduced produced[kFzMultiMax];
+    int n_produced;
+    int last_order[kFzMultiMax], last_n, last_consumers, last_keep;   // the layout of the last multi-job launch (fz_diag_multi_last)
     // device allocations replaced by a larger one while a captured graph may still hold their address: kept until
     // fz_ctx_destroy (a replay must never touch freed memory)
     int graphs_captured;
@@ -130,11 +145,10 @@ struct FzRagged {
 };
 
 // the job table of one fz_ntt_multi launch travels in the kernarg segment (no device copy, capturable in a graph)
-constexpr int kFzMultiMax = 32;
 struct FzMultiJobs {
     const int32_t *in[kFzMultiMax];
     int32_t *out[kFzMultiMax];
-    unsigned end[kFzMultiMax];   // running total of WORKGROUPS up to and including job j (filled by fz_launch_ntt_multi)
+    unsigned end[kFzMultiMax];   // running total of WORKGROUPS up to and including job j (the radix-4 path fills it; the 16-per-lane path its own permuted copy)
     unsigned rows[kFzMultiMax];  // rows of job j; bit 31 set: inverse transform
     int n;
 };
@@ -170,7 +184,12 @@ int fz_retire(fz_ctx *ctx, void *d_ptr, const char *what);       // hipFree, or 
 // launchers (fz_ntt.hip)
 int fz_launch_ntt(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch, bool inverse);
 int fz_ntt_query_grid(fz_ctx *ctx);
-int fz_launch_ntt_multi(fz_ctx *ctx, FzMultiJobs &jobs);           // degree 64 / 256; fills jobs.end
+int fz_launch_ntt_multi(fz_ctx *ctx, FzMultiJobs &jobs);           // degree 64 / 256; the radix-4 path fills jobs.end
+// the layout of a 16-per-lane multi-job launch: order[k] = the table entry that runs k-th (the first *consumers of them read what
+// `prev` wrote), end[k] = workgroups up to and including it, for `resident` workgroups on the chip at once, *keep = the direction
+// whose outputs store normally (0 none, 1 forward, 2 inverse); -> workgroups in all
+unsigned fz_multi_plan(const FzMultiJobs &J, int degree, const FzProduced *prev, int n_prev, bool ordered, unsigned resident, int *order,
+                       unsigned *end, int *consumers, int *keep);
 int fz_launch_diag_clock(hipStream_t stream, unsigned long long ticks, unsigned long long *d_out);
 int fz_launch_diag(fz_ctx *ctx, int what, const void *src, void *dst, size_t bytes);
 

@@ -113,15 +113,30 @@ __device__ __forceinline__ void nt_store4(int32_t *p, const int4 &v) {
     __builtin_nontemporal_store(t, reinterpret_cast<fz_v4i *>(p));
 }
 
-// the task's 4 coalesced 16-byte stores (same scalar split as chunk_load: only a ragged last chunk predicates its lanes)
+// the same as a normal store: for outputs the NEXT launch of the stream transforms (ntt_jobs16, fz_multi_plan)
+__device__ __forceinline__ void plain_store4(int32_t *p, const int4 &v) {
+    fz_v4i t = {v.x, v.y, v.z, v.w};
+    *reinterpret_cast<fz_v4i *>(p) = t;
+}
+
+// the task's 4 coalesced 16-byte stores (same scalar split as chunk_load: only a ragged last chunk predicates its lanes);
+// PLAIN: normal instead of streaming stores (ntt_jobs16_keep)
+template <bool PLAIN = false>
 __device__ __forceinline__ void chunk_store(int32_t *out, size_t task, size_t total, int lane, const int4 &o0, const int4 &o1,
                                             const int4 &o2, const int4 &o3) {
     if ((task + 1) * kChunk <= total) {
         int32_t *b = out + task * kChunk;
-        nt_store4(b + 4 * lane, o0);
-        nt_store4(b + 4 * lane + 256, o1);
-        nt_store4(b + 4 * lane + 512, o2);
-        nt_store4(b + 4 * lane + 768, o3);
+        if constexpr (PLAIN) {
+            plain_store4(b + 4 * lane, o0);
+            plain_store4(b + 4 * lane + 256, o1);
+            plain_store4(b + 4 * lane + 512, o2);
+            plain_store4(b + 4 * lane + 768, o3);
+        } else {
+            nt_store4(b + 4 * lane, o0);
+            nt_store4(b + 4 * lane + 256, o1);
+            nt_store4(b + 4 * lane + 512, o2);
+            nt_store4(b + 4 * lane + 768, o3);
+        }
     } else {
         const size_t base = task * kChunk + 4 * lane;
         if (base < total) nt_store4(out + base, o0);
@@ -265,7 +280,7 @@ __device__ __forceinline__ void inv16_passes(double (&a)[16], double *row, const
 
 // the whole forward kernel as a function of (block index, blocks that share the batch): ntt_fwd16 runs it over the grid,
 // ntt_jobs16 over the run of workgroups a job owns
-template <int LOGD, bool FAST>
+template <int LOGD, bool FAST, bool PLAIN = false>
 __device__ __forceinline__ void fwd16_run(const int32_t *in, int32_t *out, size_t batch, unsigned block, unsigned nblocks, double *lds,
                                           const double2 *__restrict__ twB, const FzTwA &twA, const FzMod &m) {
     using G = Geom<LOGD>;
@@ -338,7 +353,7 @@ __device__ __forceinline__ void fwd16_run(const int32_t *in, int32_t *out, size_
         const int4 o3 = *reinterpret_cast<const int4 *>(stage + pad4(768 + 4 * lane));
         wave_sync();
         if (more) chunk_to_lds(stage, lane, raw);   // waits for the prefetched loads (no store is younger)
-        chunk_store(out, task, total, lane, o0, o1, o2, o3);
+        chunk_store<PLAIN>(out, task, total, lane, o0, o1, o2, o3);
     };
     size_t task = first;
     for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
@@ -355,7 +370,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void ntt_fwd16(const int32_t *
 // ------------------------------------------------------------------------------------------
 // inverse: contiguous pass -> transpose -> strided pass (n^{-1} folded into the last stage)
 // ------------------------------------------------------------------------------------------
-template <int LOGD, bool FAST>
+template <int LOGD, bool FAST, bool PLAIN = false>
 __device__ __forceinline__ void inv16_run(const int32_t *in, int32_t *out, size_t batch, unsigned block, unsigned nblocks, double *lds,
                                           const double2 *__restrict__ itwB, const FzTwA &twA, const FzMod &m) {
     using G = Geom<LOGD>;
@@ -406,7 +421,7 @@ __device__ __forceinline__ void inv16_run(const int32_t *in, int32_t *out, size_
         const int4 o3 = *reinterpret_cast<const int4 *>(stage + pad4(768 + 4 * lane));
         wave_sync();
         if (more) chunk_to_lds(stage, lane, raw);
-        chunk_store(out, task, total, lane, o0, o1, o2, o3);
+        chunk_store<PLAIN>(out, task, total, lane, o0, o1, o2, o3);
     };
     size_t task = first;
     for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
@@ -825,6 +840,33 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void ntt_jobs16(JT J, const do
     const size_t rows = rw & 0x7fffffffu;
     if ((rw >> 31) != 0) inv16_run<LOGD, FAST>(in, out, rows, blockIdx.x - first, last - first, lds, itwB, itwA, m);
     else fwd16_run<LOGD, FAST>(in, out, rows, blockIdx.x - first, last - first, lds, twB, twA, m);
+    if (stamp && threadIdx.x < 64) {                                    // fz_diag_stamps_*: see ntt_jobs4
+        __builtin_amdgcn_s_waitcnt(0);
+        const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+        if (threadIdx.x == 0) {
+            stamp[2 * (size_t)blockIdx.x] = t0;
+            stamp[2 * (size_t)blockIdx.x + 1] = t1;
+        }
+    }
+}
+
+// ntt_jobs16 for a launch whose outputs of ONE direction are the stream's next launch's inputs (fz_multi_plan): KEEP = 1, the
+// forward jobs store normally instead of streaming so that their lines stay in the caches, KEEP = 2, the inverse jobs do.  A
+// kernel of its own with two job bodies, like ntt_jobs16 (which is untouched: tables without consumers run exactly what they
+// ran before): one kernel holding both store kinds of both bodies, chosen by a flag in the table, ran 2 % slower on EVERY path,
+// and a wave-uniform run-time branch around the stores 2.5 % (profiles/r08_multi_order_ab.txt).
+template <int LOGD, bool FAST, typename JT, int KEEP>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void ntt_jobs16_keep(JT J, const double2 *__restrict__ twB, const double2 *__restrict__ itwB,
+                                                                       FzTwA twA, FzTwA itwA, FzMod m, unsigned long long *stamp) {
+    __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    unsigned first, last, rw;
+    const int32_t *in;
+    int32_t *out;
+    pick_job(J, blockIdx.x, first, last, rw, in, out);
+    const size_t rows = rw & 0x7fffffffu;
+    if ((rw >> 31) != 0) inv16_run<LOGD, FAST, KEEP == 2>(in, out, rows, blockIdx.x - first, last - first, lds, itwB, itwA, m);
+    else fwd16_run<LOGD, FAST, KEEP == 1>(in, out, rows, blockIdx.x - first, last - first, lds, twB, twA, m);
     if (stamp && threadIdx.x < 64) {                                    // fz_diag_stamps_*: see ntt_jobs4
         __builtin_amdgcn_s_waitcnt(0);
         const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
@@ -2260,35 +2302,102 @@ static void launch_jobs(fz_ctx *ctx, FzMultiJobs &J, hipEvent_t e0, hipEvent_t e
 }
 
 // the 16-per-lane form of a multi-job launch: job j gets min(its workgroups, its share of the resident grid) workgroups
-template <int LOGD, bool FAST, int NJ>
+template <int LOGD, bool FAST, int NJ, int KEEP>
 static void launch_jobs16_n(fz_ctx *ctx, const FzMultiJobs &J, unsigned total, hipEvent_t e0, hipEvent_t e1, unsigned long long *stamp) {
     FzJobsN<NJ> S;
     for (int j = 0; j < NJ; ++j) { S.in[j] = J.in[j]; S.out[j] = J.out[j]; S.end[j] = J.end[j]; S.rows[j] = J.rows[j]; }
-    hipExtLaunchKernelGGL((ntt_jobs16<LOGD, FAST, FzJobsN<NJ>>), dim3(total), dim3(64 * kWavesPerBlock), 0, ctx->stream, e0, e1, 0, S,
-                          (const double2 *)ctx->d_twB, (const double2 *)ctx->d_itwB, ctx->twA, ctx->itwA, ctx->mod, stamp);
+    if constexpr (KEEP == 0)
+        hipExtLaunchKernelGGL((ntt_jobs16<LOGD, FAST, FzJobsN<NJ>>), dim3(total), dim3(64 * kWavesPerBlock), 0, ctx->stream, e0, e1, 0, S,
+                              (const double2 *)ctx->d_twB, (const double2 *)ctx->d_itwB, ctx->twA, ctx->itwA, ctx->mod, stamp);
+    else
+        hipExtLaunchKernelGGL((ntt_jobs16_keep<LOGD, FAST, FzJobsN<NJ>, KEEP>), dim3(total), dim3(64 * kWavesPerBlock), 0, ctx->stream, e0, e1,
+                              0, S, (const double2 *)ctx->d_twB, (const double2 *)ctx->d_itwB, ctx->twA, ctx->itwA, ctx->mod, stamp);
+}
+
+// The layout of a 16-per-lane multi-job launch (host only; fz_diag_multi_order shows it to the tests).
+// A launch that transforms what the context's previous multi-job launch wrote (the software-pipelined step: forward of the next
+// batches beside the inverse of the last ones) re-reads those bytes one launch later.  Workgroups take their slots in blockIdx
+// order -- with two chains in flight a launch's workgroups enter over half its duration -- so the jobs' runs of workgroups are laid
+// out in the order the launch should do its work: first the CONSUMERS, the jobs whose input is an output of the previous launch
+// (rows <= the rows written), the most recently written first, then the other jobs in table order: what this launch writes for the
+// next one is written last and read first.  In such a launch the other jobs are taken for producers of the next launch and, when
+// they all have one direction and no consumer shares it, store normally (ntt_jobs16_keep) so that their lines stay in the
+// caches; consumers, and every job of a table without consumers, keep the streaming stores, and such a table its table order and
+// the very kernel of rounds 5-6.  Workgroups per job are unchanged:
+// min(its workgroups, its share of the resident grid); more, shorter-lived generations of workgroups sharpen the order and cost
+// more in start-ups than the order brings (profiles/r08_multi_order_ab.txt).
+// *keep: whose outputs store normally -- the producers' direction (1 forward, 2 inverse) when there are consumers, the producers
+// all have one direction and no consumer shares it (the kernel chooses the store kind by direction), else 0.  (Only whole chunks
+// of a kept job store normally: a ragged last chunk, at most 4 KiB of a job, streams as before.)
+unsigned fz_multi_plan(const FzMultiJobs &J, int degree, const FzProduced *prev, int n_prev, bool ordered, unsigned resident, int *order,
+                       unsigned *end, int *consumers, int *keep) {
+    auto tasks_of = [&](int j) { return ((size_t)(J.rows[j] & 0x7fffffffu) * (size_t)degree + kChunk - 1) / kChunk; };
+    bool taken[kFzMultiMax] = {};
+    int n = 0;
+    if (ordered)
+        for (int k = n_prev - 1; k >= 0; --k)                                // the most recently produced first
+            for (int j = 0; j < J.n; ++j) {
+                const unsigned rows = J.rows[j] & 0x7fffffffu;
+                if (taken[j] || rows == 0 || J.in[j] != prev[k].out || rows > prev[k].rows) continue;
+                taken[j] = true;
+                order[n++] = j;
+            }
+    *consumers = n;
+    for (int j = 0; j < J.n; ++j)
+        if (!taken[j]) order[n++] = j;
+    size_t all_tasks = 0;
+    for (int j = 0; j < J.n; ++j) all_tasks += tasks_of(j);
+    unsigned total = 0;
+    for (int k = 0; k < J.n; ++k) {
+        const size_t tasks = tasks_of(order[k]);
+        const size_t blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
+        size_t share = all_tasks ? ((size_t)resident * tasks + all_tasks - 1) / all_tasks : 0;   // proportional, rounded up, at least one
+        if (share < 1) share = 1;
+        total += (unsigned)(tasks ? std::min(blocks, share) : 0);
+        end[k] = total;
+    }
+    unsigned dirs_cons = 0, dirs_prod = 0;                                  // bit 0: forward jobs among them, bit 1: inverse jobs
+    for (int k = 0; k < J.n; ++k) (k < *consumers ? dirs_cons : dirs_prod) |= 1u << (J.rows[order[k]] >> 31);
+    *keep = *consumers > 0 && (dirs_prod == 1 || dirs_prod == 2) && (dirs_cons & dirs_prod) == 0 ? (int)dirs_prod : 0;
+    return total;
+}
+
+// what the launch just issued wrote, in the order it ran (order == nullptr: table order), and the layout it ran in
+// (fz_diag_multi_last)
+static void record_produced(fz_ctx *ctx, const FzMultiJobs &J, const int *order, int consumers, int keep) {
+    ctx->last_n = J.n; ctx->last_consumers = consumers; ctx->last_keep = keep;
+    for (int k = 0; k < J.n; ++k) ctx->last_order[k] = order ? order[k] : k;
+    ctx->n_produced = 0;
+    if (!ctx->knob_multi_order) return;
+    for (int k = 0; k < J.n; ++k) {
+        const int j = order ? order[k] : k;
+        ctx->produced[ctx->n_produced++] = FzProduced{J.out[j], J.rows[j] & 0x7fffffffu};
+    }
 }
 
 template <int LOGD, bool FAST>
-static int launch_jobs16(fz_ctx *ctx, FzMultiJobs &J, hipEvent_t e0, hipEvent_t e1) {
-    constexpr size_t D = (size_t)1 << LOGD;
-    size_t all_tasks = 0;
-    for (int j = 0; j < J.n; ++j) all_tasks += ((J.rows[j] & 0x7fffffffu) * D + kChunk - 1) / kChunk;
-    const size_t cap = (size_t)std::min(ctx->grid_fwd, ctx->grid_inv);      // workgroups the chip holds at once
-    unsigned total = 0;
-    for (int j = 0; j < J.n; ++j) {
-        const size_t tasks = ((J.rows[j] & 0x7fffffffu) * D + kChunk - 1) / kChunk;
-        const size_t blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
-        size_t share = (cap * tasks + all_tasks - 1) / all_tasks;            // proportional, rounded up, at least one
-        if (share < 1) share = 1;
-        total += (unsigned)(tasks ? std::min(blocks, share) : 0);
-        J.end[j] = total;
-    }
-    for (int j = J.n; j < kFzMultiMax; ++j) { J.end[j] = total; J.rows[j] = 0; J.in[j] = nullptr; J.out[j] = nullptr; }
+static int launch_jobs16(fz_ctx *ctx, const FzMultiJobs &J, hipEvent_t e0, hipEvent_t e1) {
+    const unsigned cap = (unsigned)std::min(ctx->grid_fwd, ctx->grid_inv);  // workgroups the chip holds at once
+    int order[kFzMultiMax];
+    FzMultiJobs P;                                                           // the table in execution order (the caller's is left alone)
+    int consumers = 0, keep = 0;
+    const unsigned total = fz_multi_plan(J, 1 << LOGD, ctx->produced, ctx->n_produced, ctx->knob_multi_order != 0, cap, order, P.end,
+                                         &consumers, &keep);
+    P.n = J.n;
+    for (int k = 0; k < J.n; ++k) { P.in[k] = J.in[order[k]]; P.out[k] = J.out[order[k]]; P.rows[k] = J.rows[order[k]]; }
+    for (int k = J.n; k < kFzMultiMax; ++k) { P.end[k] = total; P.rows[k] = 0; P.in[k] = nullptr; P.out[k] = nullptr; }
     if (total == 0) return FZ_OK;
     unsigned long long *stamp = stamp_slots(ctx, total);
-    if (J.n <= 4) launch_jobs16_n<LOGD, FAST, 4>(ctx, J, total, e0, e1, stamp);
-    else if (J.n <= 8) launch_jobs16_n<LOGD, FAST, 8>(ctx, J, total, e0, e1, stamp);
-    else launch_jobs16_n<LOGD, FAST, kFzMultiMax>(ctx, J, total, e0, e1, stamp);
+    auto by_size = [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if (J.n <= 4) launch_jobs16_n<LOGD, FAST, 4, KP>(ctx, P, total, e0, e1, stamp);
+        else if (J.n <= 8) launch_jobs16_n<LOGD, FAST, 8, KP>(ctx, P, total, e0, e1, stamp);
+        else launch_jobs16_n<LOGD, FAST, kFzMultiMax, KP>(ctx, P, total, e0, e1, stamp);
+    };
+    if (keep == 1) by_size(std::integral_constant<int, 1>());
+    else if (keep == 2) by_size(std::integral_constant<int, 2>());
+    else by_size(std::integral_constant<int, 0>());
+    record_produced(ctx, J, order, consumers, keep);
     return fz_check_hip(hipGetLastError(), "ntt_jobs16 launch");
 }
 
@@ -2330,10 +2439,12 @@ static int launch_jobs_f(fz_ctx *ctx, FzMultiJobs &J) {
     }
     else if (nr == 2) launch_jobs<LOGD, FAST, 2, 2>(ctx, J, e0, e1);    // (4 or 8 waves per workgroup: 6.11 / 6.04 us against 5.99 for the two-job launch)
     else launch_jobs<LOGD, FAST, 4, 2>(ctx, J, e0, e1);
+    record_produced(ctx, J, nullptr, 0, 0);                                  // (one wave-task per wave: the grid runs in table order)
     return fz_check_hip(hipGetLastError(), "ntt_jobs4 launch");
 }
 
-// J.in / J.out / J.rows (bit 31: inverse) / J.n filled by the caller; J.end is computed here (workgroups per job)
+// J.in / J.out / J.rows (bit 31: inverse) / J.n filled by the caller; J.end (workgroups per job) is computed here by the radix-4
+// path only: the 16-per-lane path leaves J alone and lays out a permuted copy of it (fz_multi_plan)
 int fz_launch_ntt_multi(fz_ctx *ctx, FzMultiJobs &J) {
     if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "multi-job transform: degree 64 or 256 only");
     if (J.n <= 0) return FZ_OK;

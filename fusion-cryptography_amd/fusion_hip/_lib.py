@@ -184,6 +184,9 @@ SIGNATURES.update({
     "fz_diag_shader_clock": (c_int, [_ctx, ctypes.c_uint, POINTER(ctypes.c_double)]),
     "fz_diag_ntt_schedule": (c_int, [_ctx, c_size_t, POINTER(c_int)]),
     "fz_diag_delay": (c_int, [_ctx, c_uint32]),
+    "fz_diag_multi_order": (c_int, [POINTER(NttJob), c_size_t, POINTER(NttJob), c_size_t, c_int, c_uint32, c_int, POINTER(c_int),
+                                    POINTER(c_uint32), POINTER(c_int), POINTER(c_int)]),
+    "fz_diag_multi_last": (c_int, [_ctx, POINTER(c_int), c_size_t, POINTER(c_size_t), POINTER(c_int), POINTER(c_int)]),
 })
 
 

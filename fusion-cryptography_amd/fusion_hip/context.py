@@ -212,6 +212,13 @@ class Context:
         check(self._lib, self._lib.fz_diag_ntt_schedule(self._h, int(rows), byref(fam)))
         return fam.value
 
+    def diag_multi_last(self):
+        """-> (order, consumers, keep) of this context's last ntt_multi_dev launch: the table entries in the order they ran, how many of
+        them read what the launch before wrote, the direction whose outputs stored normally (0 none, 1 forward, 2 inverse)"""
+        order, n, cons, keep = (c_int * 32)(), ctypes.c_size_t(), c_int(), c_int()
+        check(self._lib, self._lib.fz_diag_multi_last(self._h, order, 32, byref(n), byref(cons), byref(keep)))
+        return list(order)[:n.value], cons.value, keep.value
+
     def diag_delay(self, microseconds):
         """one wave that occupies this context's stream for `microseconds` (asynchronous, capturable)"""
         check(self._lib, self._lib.fz_diag_delay(self._h, int(microseconds)))

@@ -61,6 +61,19 @@ FZ_API int fz_diag_shader_clock(fz_ctx *ctx, unsigned microseconds, double *out_
  * ntt_jobs16) or 0 (another kernel: degrees outside 32..256).  What bench.py names its dominant kernel by, instead of mirroring
  * the library's crossover. */
 FZ_API int fz_diag_ntt_schedule(fz_ctx *ctx, size_t rows, int *family);
+/* The layout fz_ntt_multi gives a launch of the 16-per-lane schedule (host arithmetic only: no context, no device): h_jobs is the
+ * table of the launch, h_prev the jobs of the context's previous multi-job launch in the order THEY ran (d_out and rows are read).
+ * h_order[k] = the entry of h_jobs that runs k-th: first the consumers -- the jobs whose d_in is a d_out of h_prev (rows <= the rows
+ * written there), the most recently written first -- then the others in table order; `ordered` = 0 (what FZ_MULTI_ORDER=0
+ * selects): table order, no consumers.  h_end[k] = workgroups of the launch up to and including that job, for
+ * `resident_workgroups` workgroups on the chip at once.  *out_consumers (optional): how many of them are consumers; when there is
+ * one, the jobs after them are taken for the next launch's producers.  *out_keep (optional): the direction whose jobs store normally
+ * instead of streaming -- 1 forward, 2 inverse: the producers' direction when they all have one and no consumer shares it -- else 0. */
+FZ_API int fz_diag_multi_order(const fz_ntt_job *h_jobs, size_t n_jobs, const fz_ntt_job *h_prev, size_t n_prev, int degree,
+                               unsigned resident_workgroups, int ordered, int *h_order, uint32_t *h_end, int *out_consumers, int *out_keep);
+/* the layout the context's LAST fz_ntt_multi launch (degree 64 / 256) really ran in: *n its jobs, h_order[k] (up to cap) the table
+ * entry that ran k-th, *out_consumers / *out_keep as above (the radix-4 schedule: table order, 0, 0) */
+FZ_API int fz_diag_multi_last(fz_ctx *ctx, int *h_order, size_t cap, size_t *n, int *out_consumers, int *out_keep);
 /* one wave that occupies the context's stream for `microseconds` (asynchronous, capturable): a stand-in of known duration for
  * a step that cannot be run here -- bench.py uses it in place of the multi-GPU all-reduce to measure, on ONE GPU, how much of
  * an exchange step's latency its second stream hides */
