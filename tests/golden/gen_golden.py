@@ -19,6 +19,9 @@ Files
   kat.json      compact replay data extracted from the reference's own reproducible KAT CSVs  [G7]
   reference_tests.json
                 the names of the reference's test functions, per test file, in file order (tests/test_reference_case_map.py)
+  challenge_edges.npz
+                the reference's coefficient rows (hash_vk_and_int_to_bytes + decode_bytes_to_polynomial_coefficients) for the
+                fixtures of tests/_challenge_edges.py at the two scheme parameter sets (argument "challenge_edges")
 """
 import csv
 import hashlib
@@ -584,6 +587,44 @@ def gen_reference_tests():
     print("reference_tests.json written:", {k: len(v) for k, v in out.items()})
 
 
+def gen_challenge_edges():
+    """tests/_challenge_edges.py's key / digest fixtures and message fixtures through the reference's own functions: the rows
+    before the transform (ternary: int8), and a SHA-256 of the fixture arrays so that a changed builder cannot meet stale rows"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _challenge_edges as E
+    out = {}
+    for name in E.SCHEME_SETS:
+        ps = E.SETS[name]
+        params = F.fusion_setup(ps.secpar, 1)
+        assert (params.degree, params.omega_ch, params.root, params.sign_hash_dst) == (ps.degree, ps.omega_ch, ps.root, ps.sign_hash_dst)
+        sb, cb, ib = E.decode_shape(ps)
+        n = sb + cb * min(ps.degree, ps.omega_ch) + ps.degree * ib           # as hash_ch asks for
+
+        def key_of(vk):
+            def P(v):
+                return PolyN(modulus=params.modulus, degree=params.degree, root=params.root, inv_root=params.inv_root,
+                             root_order=params.root_order, values=[int(t) for t in v])
+            return F.OneTimeVerificationKey(left_vk_hat=GeneralMatrix(matrix=[[P(vk[0])]]),
+                                            right_vk_hat=GeneralMatrix(matrix=[[P(vk[1])]]))
+
+        def row_of(vk, i):
+            b = F.hash_vk_and_int_to_bytes(params, key_of(vk), i, n)
+            return F.decode_bytes_to_polynomial_coefficients(b, params.secpar, params.modulus, params.degree, params.beta_ch,
+                                                             params.omega_ch)
+        fx = E.fixtures(name)
+        rows = np.array([row_of(fx.vk[k], fx.ints[k]) for k in range(len(fx))], dtype=np.int64)
+        mvk = E.message_keys(ps)
+        msgs = [m for _, m in E.message_fixtures()]
+        mrows = np.array([row_of(mvk[k], F.hash_message_to_int(params, m)) for k, m in enumerate(msgs)], dtype=np.int64)
+        assert np.abs(rows).max() <= 1 and np.abs(mrows).max() <= 1
+        out[f"rows_{name}"] = rows.astype(np.int8)
+        out[f"message_rows_{name}"] = mrows.astype(np.int8)
+        out[f"fixtures_sha256_{name}"] = np.array(fx.sha256())
+        out[f"messages_sha256_{name}"] = np.array(E.messages_sha256(ps))
+    np.savez_compressed(os.path.join(HERE, "challenge_edges.npz"), **out)
+    print("challenge_edges.npz written:", {k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["algebra", "bulk", "scheme", "kat", "many", "kat_flow", "reference_tests"]
     if "full" in sys.argv[1:]:                  # ~5 minutes on 8 cores: only on request
@@ -608,3 +649,5 @@ if __name__ == "__main__":
         gen_kat()
     if "reference_tests" in which:
         gen_reference_tests()
+    if "challenge_edges" in which:
+        gen_challenge_edges()

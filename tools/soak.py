@@ -183,6 +183,17 @@ while time.time() < t_end:
         ctx = cctx[int(rng.integers(0, len(cctx)))]
         dv, dc = DB.from_numpy(ctx, vk), DB(ctx, nn * d * 4)
         if rng.random() < 0.5:
+            # a few digests replaced by integers of a random digit count (a SHA3-256 digest has 76-78 digits: the decimal
+            # conversion would never see fewer chunks or a narrow top chunk), expected through the host pipeline's pieces
+            nbytes = 8 * 1024 * 2
+            for i in rng.choice(nn, size=min(nn, 3), replace=False):
+                digits = int(rng.integers(1, 78))
+                val = int(rng.integers(1, 10)) * 10 ** (digits - 1) + int(rng.integers(0, 2**62)) % 10 ** (digits - 1)
+                if rng.random() < 0.3:
+                    val -= val % 10 ** int(rng.integers(0, digits))                     # zero chunks below the top
+                pre[i] = np.frombuffer(val.to_bytes(32, "little"), dtype=np.uint8)
+                text = bytes(HP.sign_hash_dst) + b"," + hostpipe.format_vk(HP, vk[i, 0], vk[i, 1]).encode() + b"," + str(val).encode()
+                coefs[i] = hostpipe.decode_coefficients(hostpipe.shake256(text, nbytes), HP.secpar, q, d, prm.beta_ch, prm.omega_ch)
             ctx.challenge_dev(HP, dv.ptr, pre, nn, dc.ptr, transform=True)
         else:                                       # the messages hashed on the device as well
             blob, off = hostpipe._pack_messages(msgs)
