@@ -283,7 +283,7 @@ static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint
         c->twA.w1_n_inv2 = 0.0;
         c->itwA.w1_n_inv2 = c->itwA.w1_n_inv * c->mod.kq;
 
-        // per-lane tables of the contiguous pass ([NE][L]); see fz_ntt.hip / tools/ntt_layout_model.py
+        // per-lane tables of the contiguous pass ([NE][L]); see fz_ntt_dev.h / tools/ntt_layout_model.py
         if (k >= 5 && k <= 8) {
             const int L = n / 16, SB = k - 4, NE = 16 - (16 >> SB);
             nB = (size_t)NE * L * 2;                       // (w, w * K / q) pairs
@@ -345,7 +345,7 @@ static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint
         c->knob_shake_full = knob("FZ_SHAKE_FORM");
         c->knob_verify_ordered = knob("FZ_VERIFY_ORDERED");
         // The fence-free cross-workgroup combine of verify_fused (relaxed agent-scope atomics on the library's own
-        // coarse-grained scratch, ordered by data dependence: csrc/fz_ntt.hip) is an argument about THIS chip's memory-side
+        // coarse-grained scratch, ordered by data dependence: csrc/fz_scheme_fused.hip) is an argument about THIS chip's memory-side
         // atomics; anything that does not report gfx950 gets the acquire/release instantiation.
         if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) c->knob_verify_ordered = 1;
         c->knob_unfused = knob("FZ_UNFUSED");

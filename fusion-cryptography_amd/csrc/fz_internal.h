@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <mutex>
+#include <type_traits>
 #include "fz_arith.h"
 
 // Wave-uniform twiddles of the strided pass, passed BY VALUE so they live in the kernarg
@@ -169,7 +170,7 @@ struct fz_graph {
     int device;
 };
 
-// largest transform length: up to 256 the register / LDS schedules of fz_ntt.hip, beyond it one workgroup per polynomial through LDS
+// largest transform length: up to 256 the register / LDS schedules of fz_ntt_dev.h, beyond it one workgroup per polynomial through LDS
 constexpr int kFzMaxDegree = 4096;
 
 // error plumbing (fz_capi.hip)
@@ -181,9 +182,30 @@ int fz_verify_scratch(fz_ctx *ctx, size_t groups, size_t doubles_per_group, doub
 int fz_agg_scratch(fz_ctx *ctx, size_t tiles, size_t tile_words, unsigned long long **acc);
 int fz_retire(fz_ctx *ctx, void *d_ptr, const char *what);       // hipFree, or keep until destroy when graphs were captured
 
-// launchers (fz_ntt.hip)
+// The host dispatch on (degree, multiply form), written once: f(std::integral_constant<int, LOGD>, std::bool_constant<FAST>) for
+// the context's degree, when it is one of 2^LOGDS, and its modulus' multiply form (4-op pseudo-Mersenne when mod.fast) -> what f
+// returns; `other` when the degree is none of them.  f is instantiated for the named degrees only, in both forms.
+template <int... LOGDS, class F>
+int fz_dispatch(const fz_ctx *ctx, int other, F &&f) {
+    int rc = other;
+    (void)((ctx->logd == LOGDS && ((rc = ctx->mod.fast ? f(std::integral_constant<int, LOGDS>(), std::true_type())
+                                                       : f(std::integral_constant<int, LOGDS>(), std::false_type())), true)) || ...);
+    return rc;
+}
+
+// how many workgroups of `kernel` (`threads` each, static LDS only) the chip holds at once, at least one per CU: the resident
+// grid a persistent kernel is capped at
+template <class K>
+int fz_resident_grid(const fz_ctx *ctx, K kernel, int threads, const char *what, int *grid) {
+    int n = 0;
+    const int rc = fz_check_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0), what);
+    if (rc == 0) *grid = (n < 1 ? 1 : n) * ctx->num_cu;       // (0: FZ_OK)
+    return rc;
+}
+
+// transforms (fz_ntt.hip)
 int fz_launch_ntt(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch, bool inverse);
-int fz_ntt_query_grid(fz_ctx *ctx);
+int fz_ntt_query_grid(fz_ctx *ctx);                                // resident grids of the 16-per-lane transforms and of the records kernels
 int fz_launch_ntt_multi(fz_ctx *ctx, FzMultiJobs &jobs);           // degree 64 / 256; the radix-4 path fills jobs.end
 // the layout of a 16-per-lane multi-job launch: order[k] = the table entry that runs k-th (the first *consumers of them read what
 // `prev` wrote), end[k] = workgroups up to and including it, for `resident` workgroups on the chip at once, *keep = the direction
@@ -192,6 +214,26 @@ unsigned fz_multi_plan(const FzMultiJobs &J, int degree, const FzProduced *prev,
                        unsigned *end, int *consumers, int *keep);
 int fz_launch_diag_clock(hipStream_t stream, unsigned long long ticks, unsigned long long *d_out);
 int fz_launch_diag(fz_ctx *ctx, int what, const void *src, void *dst, size_t bytes);
+
+// fused products (fz_polymul.hip)
+int fz_launch_polymul_fused(fz_ctx *ctx, const int32_t *f, const int32_t *g, int32_t *out, size_t batch);
+bool fz_polymul16_ok(const fz_ctx *ctx, const int32_t *f, const int32_t *g, const int32_t *out, size_t batch);
+
+// compact byte encoding (fz_records.hip; degree 64 / 256): n records of rows * degree values, w-bit fields u = z + bound; encode (decode =
+// false) rows -> bytes, decode bytes -> rows; d_status [n] cleared, then 0 or FZ_VERDICT_NORM / FZ_VERDICT_ENCODING; failed records zeroed
+int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
+                      int *d_status);
+int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_rec (fz_ntt_query_grid calls it)
+
+// fused keygen and verification (fz_scheme_fused.hip)
+int fz_launch_keygen_fused(fz_ctx *ctx, const int32_t *A, const int32_t *coef, int32_t *sk_hat, int32_t *vk, size_t segments,
+                           int l, bool broadcast = false);
+int fz_launch_verify_fused_i64(fz_ctx *ctx, const int32_t *A, const int64_t *sig, size_t sig_stride, const int64_t *target,
+                               size_t target_stride, size_t groups, int l, int64_t beta, int64_t omega, int *d_verdict);
+int fz_launch_verify_fused(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *target, size_t groups, int l,
+                           int64_t beta, int64_t omega, int *d_verdict);
+int fz_launch_verify_signatures(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *vk, const int32_t *c, size_t N,
+                                int l, int64_t beta, int64_t omega, int *d_verdict);
 
 // challenge pipeline on the device (fz_challenge.hip) and the pieces it shares with the host serialiser (fz_host.cpp)
 struct fz_scheme_params;
@@ -213,24 +255,9 @@ void fz_host_vk_text_parts(const fz_scheme_params *P, char *s0, int *n0, char *s
 size_t fz_host_challenge_needed_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes);
 bool fz_host_params_ok(const fz_scheme_params *P);
 
-int fz_launch_polymul_fused(fz_ctx *ctx, const int32_t *f, const int32_t *g, int32_t *out, size_t batch);
-bool fz_polymul16_ok(const fz_ctx *ctx, const int32_t *f, const int32_t *g, const int32_t *out, size_t batch);
-int fz_launch_keygen_fused(fz_ctx *ctx, const int32_t *A, const int32_t *coef, int32_t *sk_hat, int32_t *vk, size_t segments,
-                           int l, bool broadcast = false);
+// launchers (fz_pointwise.hip)
 int fz_launch_fill_synthetic(fz_ctx *ctx, int32_t *out, size_t count, unsigned long long seed);
 int fz_launch_bcast_rows(fz_ctx *ctx, const int32_t *in, int32_t *out, size_t segments, int l);
-int fz_launch_verify_fused_i64(fz_ctx *ctx, const int32_t *A, const int64_t *sig, size_t sig_stride, const int64_t *target,
-                               size_t target_stride, size_t groups, int l, int64_t beta, int64_t omega, int *d_verdict);
-int fz_launch_verify_fused(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *target, size_t groups, int l,
-                           int64_t beta, int64_t omega, int *d_verdict);
-int fz_launch_verify_signatures(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *vk, const int32_t *c, size_t N,
-                                int l, int64_t beta, int64_t omega, int *d_verdict);
-// compact byte encoding (degree 64 / 256): n records of rows * degree values, w-bit fields u = z + bound; encode (decode = false)
-// rows -> bytes, decode bytes -> rows; d_status [n] cleared, then 0 or FZ_VERDICT_NORM / FZ_VERDICT_ENCODING; failed records zeroed
-int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
-                      int *d_status);
-
-// launchers (fz_pointwise.hip)
 enum { FZ_OP_MUL = 0, FZ_OP_ADD = 1, FZ_OP_SUB = 2, FZ_OP_NEG = 3, FZ_OP_MULACC = 4 };
 int fz_launch_pw(fz_ctx *ctx, int op, const int32_t *a, const int32_t *b, int32_t *out, size_t count);
 int fz_launch_pw_bcast(fz_ctx *ctx, const int32_t *a, const int32_t *s, int32_t *out, size_t rows);

@@ -1,0 +1,411 @@
+// fz_records.hip -- the compact byte encoding of keys, signatures and aggregates: the records_* kernels on the chunk walk and
+// the passes of the 16-per-lane transforms (fz_ntt_dev.h), their launcher and their resident-grid query.
+#include "fz_ntt_dev.h"
+#include "../../include/fusion_hip.h"
+
+namespace {
+// ------------------------------------------------------------------------------------------
+// Compact byte encoding of records (not in the reference).  A record is `rows` rows of D values; each
+// value becomes a w-bit field u = z + B (z centred, B the kind's bound, w = bit_length(2B)), fields row-major and LSB first.
+// Coefficient-domain kinds (COEF: signatures, aggregates) carry z = cent(INTT(row)); verification keys z = cent(row).
+// The transform kernels' chunk walk: one wave-task is one 1024-value chunk of the batch, i.e. 1024 fields = 128 * w bytes = 8 * w
+// 16-byte units of the byte stream (the chunk of task t starts at byte 128 * w * t, always 16-byte aligned).  Lane `lane` owns the
+// chunk's values 16 * lane .. 16 * lane + 15, i.e. w consecutive 16-bit words of the packed chunk; a record is a multiple of 16
+// values, so a lane's fields never straddle two records.  Staging per wave: the int32 image of chunk_load at the start of the
+// wave's transpose region, the packed chunk (at most 4 KiB, w <= 32) right behind it: together exactly the region, so the LDS of
+// a workgroup is that of the transforms (lds16_doubles).  w and B are kernel arguments: every branch on them is wave-uniform.
+// ------------------------------------------------------------------------------------------
+constexpr int kPackOff = kStageWords * 4;            // byte offset of the packed chunk inside a wave's region
+constexpr int kPackBytes = 128 * 32;                 // 1024 fields of at most 32 bits
+static_assert(kPackOff + kPackBytes <= Geom<6>::PPW * Geom<6>::PS * 8 && kPackOff + kPackBytes <= Geom<8>::PPW * Geom<8>::PS * 8,
+              "the packed chunk must fit behind the int32 image in a wave's region");
+
+typedef int fz_v2i __attribute__((ext_vector_type(2)));
+// the wave-uniform table of the transform is read from constant memory where it is used, as polymul16 does: held in scalar
+// registers across the loop (72 of them) it leaves too few for the record walk and the field width
+typedef const __attribute__((address_space(4))) FzTwA *TabPtr;
+
+// a packed chunk in registers: unit 64 * j + lane in u[j] (8 * w <= 256 units)
+struct Packed { int4 u[4]; };
+
+// the packed chunk of `task`: units past the end of the stream are not read; the stream's last unit may be 8 bytes (a record
+// of degree 64 with rows * w odd), then it is read as such
+__device__ __forceinline__ Packed packed_load(const uint8_t *in, size_t task, size_t total_bytes, int w, int lane) {
+    Packed c;
+    const size_t base = task * 128 * (size_t)w;
+    const size_t left = total_bytes - base;
+    const unsigned cb = (unsigned)(left < (size_t)128 * w ? left : (size_t)128 * w);      // the chunk's bytes (uniform)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        c.u[j] = make_int4(0, 0, 0, 0);
+        if (64u * 16u * j < cb) {
+            const unsigned off = 16u * (64u * j + lane);
+            if (off + 16 <= cb) {
+                const fz_v4i t = __builtin_nontemporal_load(reinterpret_cast<const fz_v4i *>(in + base + off));
+                c.u[j] = make_int4(t.x, t.y, t.z, t.w);
+            } else if (off < cb) {
+                const fz_v2i t = __builtin_nontemporal_load(reinterpret_cast<const fz_v2i *>(in + base + off));
+                c.u[j] = make_int4(t.x, t.y, 0, 0);
+            }
+        }
+    }
+    return c;
+}
+
+__device__ __forceinline__ void packed_to_lds(uint8_t *pk, const Packed &c, int w, int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (64 * j < 8 * w && 64 * j + lane < 8 * w) *reinterpret_cast<int4 *>(pk + 16 * (64 * j + lane)) = c.u[j];
+}
+
+__device__ __forceinline__ Packed packed_from_lds(const uint8_t *pk, int w, int lane) {
+    Packed c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        c.u[j] = make_int4(0, 0, 0, 0);
+        if (64 * j < 8 * w && 64 * j + lane < 8 * w) c.u[j] = *reinterpret_cast<const int4 *>(pk + 16 * (64 * j + lane));
+    }
+    return c;
+}
+
+// the chunk's units to the stream (streaming stores; an 8-byte last unit as such, nothing past the end)
+__device__ __forceinline__ void packed_store(uint8_t *out, size_t task, size_t total_bytes, int w, int lane, const Packed &c) {
+    const size_t base = task * 128 * (size_t)w;
+    const size_t left = total_bytes - base;
+    const unsigned cb = (unsigned)(left < (size_t)128 * w ? left : (size_t)128 * w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (64u * 16u * j < cb) {
+            const unsigned off = 16u * (64u * j + lane);
+            if (off + 16 <= cb) {
+                fz_v4i t = {c.u[j].x, c.u[j].y, c.u[j].z, c.u[j].w};
+                __builtin_nontemporal_store(t, reinterpret_cast<fz_v4i *>(out + base + off));
+            } else if (off < cb) {
+                fz_v2i t = {c.u[j].x, c.u[j].y};
+                __builtin_nontemporal_store(t, reinterpret_cast<fz_v2i *>(out + base + off));
+            }
+        }
+    }
+}
+
+// a lane's 16 fields (u < 2^w) -> its w 16-bit words at dst.  The bit count `nb` depends on w only: the emits are uniform branches.
+__device__ __forceinline__ void fields_pack(uint16_t *dst, const uint32_t (&u)[16], int w) {
+    unsigned long long acc = 0;
+    int nb = 0, o = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        acc |= (unsigned long long)u[k] << nb;      // nb < 16: at most 47 bits held
+        nb += w;
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            if (nb >= 16) {
+                dst[o++] = (uint16_t)acc;
+                acc >>= 16;
+                nb -= 16;
+            }
+    }
+}
+
+// ... and back: the lane's w words at src -> its 16 fields (exactly w words are read)
+__device__ __forceinline__ void fields_unpack(const uint16_t *src, uint32_t (&u)[16], int w) {
+    const unsigned long long mask = (1ull << w) - 1;
+    unsigned long long acc = 0;
+    int nb = 0, o = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            if (nb < w) {
+                acc |= (unsigned long long)src[o++] << nb;
+                nb += 16;
+            }
+        u[k] = (uint32_t)(acc & mask);
+        acc >>= w;
+        nb -= w;
+    }
+}
+
+// Per-record status: every (wave, record) with a failing lane sets its record's word with ONE atomic (at most 16 records meet
+// in a chunk)
+__device__ __forceinline__ void records_flag(int *status, size_t rec, bool bad, int code, int lane) {
+    unsigned long long fail = __ballot(bad);
+    while (fail) {                                        // uniform: one round per failing record of the wave
+        const int first = __builtin_ctzll(fail);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)rec, first);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(rec >> 32), first);
+        const size_t r = ((size_t)hi << 32) | lo;
+        if (lane == first) atomicOr(status + r, code);
+        fail &= ~__ballot(rec == r);
+    }
+}
+
+// the record of a lane's first value, walked along the wave's chunks: the divisions run once per wave (constructor), a step is
+// an add, a compare and a select (per lane: the uniform state would compete with the transform's scalar operands)
+struct RecWalk {
+    size_t rec, srec;
+    unsigned off, soff, rv;
+    __device__ __forceinline__ RecWalk(size_t first, size_t stride, unsigned rec_values, int lane) : rv(rec_values) {
+        const size_t e = first * kChunk + 16 * lane, s = stride * kChunk;
+        rec = e / rv;
+        off = (unsigned)(e - rec * rv);
+        srec = s / rv;
+        soff = (unsigned)(s - srec * rv);
+        asm volatile("" : "+v"(srec), "+v"(soff), "+v"(rv));      // uniform, but VALU operands only: out of the scalar file
+    }
+    __device__ __forceinline__ void step() {
+        off += soff;                                      // < 2 * rv: no overflow, rv < 2^31
+        const unsigned c = off >= rv ? 1u : 0u;
+        rec += srec + c;
+        off -= c * rv;
+    }
+};
+
+// encode: rows [records][rec_values] int32 -> the byte stream; status word of a record |= FZ_VERDICT_NORM where some |z| > B
+template <int LOGD, bool FAST, bool COEF>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int32_t *in, uint8_t *out, size_t total, unsigned rec_values,
+                                                                      int w, int bound, int *status, const double2 *__restrict__ itwB,
+                                                                      const FzTwA *tab, FzMod m) {
+    using G = Geom<LOGD>;
+    constexpr int D = G::D, L = G::L, PPW = G::PPW, NE = G::NE, PS = G::PS;
+    constexpr int REGION = PPW * PS;
+    __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
+    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int p = lane / L, r = lane % L;
+    const size_t tasks = (total + kChunk - 1) / kChunk;
+    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
+    const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
+    Chunk raw0 = {};
+    if (first < tasks) raw0 = chunk_load(in, first, total, lane);      // before the table: see fwd16_run
+    if constexpr (COEF) {
+        for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = itwB[i];
+        __syncthreads();
+    }
+    double *region = lds + wave * REGION;
+    int32_t *stage = reinterpret_cast<int32_t *>(region);
+    uint8_t *pk = reinterpret_cast<uint8_t *>(region) + kPackOff;
+    double *row = region + p * PS;
+    if (first >= tasks) return;
+    chunk_to_lds(stage, lane, raw0);
+    RecWalk walk(first, stride, rec_values, lane);
+    unsigned two_b = 2u * (unsigned)bound, wmask = (unsigned)((1ull << w) - 1), bnd = (unsigned)bound;
+    asm volatile("" : "+v"(two_b), "+v"(wmask), "+v"(bnd));       // VALU operands only (see RecWalk)
+
+    auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {       // pipeline and peeling: see fwd16_run
+        constexpr bool more = decltype(more_tag)::value;
+        Chunk raw = {};
+        if (more) raw = chunk_load(in, task + stride, total, lane);
+        int wl = w;
+        asm volatile("" : "+s"(wl));                      // what depends on w alone (the bit offsets of the packing, the stream's
+        const size_t total_bytes = total / 8 * (size_t)wl;      // length) is recomputed per chunk, not held across the loop
+        wave_sync();
+        if constexpr (COEF) {
+            double a[16];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int4 t = *reinterpret_cast<const int4 *>(stage + pad4(16 * lane + 4 * k));
+                a[4 * k + 0] = (double)t.x;
+                a[4 * k + 1] = (double)t.y;
+                a[4 * k + 2] = (double)t.z;
+                a[4 * k + 3] = (double)t.w;
+            }
+            wave_sync();
+            TabPtr t = (TabPtr)tab;
+            asm volatile("" : "+s"(t));
+            inv16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
+            wave_sync();
+        }
+        // the lane's 16 consecutive values: centred (the transform's outputs already are), range-checked, packed
+        // |z + B| < 2^32: the high word is all ones exactly when z < -B, the low word exceeds 2B exactly when z > B
+        uint32_t u[16], hi = 0, mx = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int4 t = *reinterpret_cast<const int4 *>(stage + pad4(16 * lane + 4 * k));
+            const int v[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const long long z = COEF ? (long long)v[i] : (long long)fz_cent((double)v[i], m);
+                const unsigned long long s = (unsigned long long)(z + (long long)bnd);
+                hi |= (uint32_t)(s >> 32);
+                mx = max(mx, (uint32_t)s);
+                u[4 * k + i] = (uint32_t)s & wmask;       // a refused field stays inside its own w bits
+            }
+        }
+        const bool bad = hi != 0 || mx > two_b;
+        fields_pack(reinterpret_cast<uint16_t *>(pk) + lane * wl, u, wl);
+        wave_sync();
+        const Packed o = packed_from_lds(pk, wl, lane);
+        wave_sync();
+        if (more) chunk_to_lds(stage, lane, raw);         // waits for the prefetched loads (no store is younger)
+        packed_store(out, task, total_bytes, wl, lane, o);
+        const bool valid = task * kChunk + 16 * lane < total;
+        records_flag(status, walk.rec, bad && valid, FZ_VERDICT_NORM, lane);
+        walk.step();
+    };
+    size_t task = first;
+    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
+    iteration(task, std::false_type());
+}
+
+// decode: the byte stream -> rows [records][rec_values] int32 (NTT(z) for COEF, z otherwise); status |= FZ_VERDICT_ENCODING where
+// some field > 2B
+template <int LOGD, bool FAST, bool COEF>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void records_decode(const uint8_t *in, int32_t *out, size_t total, unsigned rec_values,
+                                                                      int w, int bound, int *status, const double2 *__restrict__ twB,
+                                                                      const FzTwA *tab, FzMod m) {
+    using G = Geom<LOGD>;
+    constexpr int D = G::D, L = G::L, PPW = G::PPW, NE = G::NE, PS = G::PS;
+    constexpr int REGION = PPW * PS;
+    __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
+    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int p = lane / L, r = lane % L;
+    const size_t tasks = (total + kChunk - 1) / kChunk;
+    const size_t total_bytes = total / 8 * (size_t)w;
+    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
+    const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
+    Packed raw0 = {};
+    if (first < tasks) raw0 = packed_load(in, first, total_bytes, w, lane);
+    if constexpr (COEF) {
+        for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
+        __syncthreads();
+    }
+    double *region = lds + wave * REGION;
+    int32_t *stage = reinterpret_cast<int32_t *>(region);
+    uint8_t *pk = reinterpret_cast<uint8_t *>(region) + kPackOff;
+    double *row = region + p * PS;
+    if (first >= tasks) return;
+    packed_to_lds(pk, raw0, w, lane);
+    RecWalk walk(first, stride, rec_values, lane);
+    const uint32_t two_b = 2u * (unsigned)bound;
+
+    auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {       // pipeline and peeling: see fwd16_run
+        constexpr bool more = decltype(more_tag)::value;
+        Packed raw = {};
+        if (more) raw = packed_load(in, task + stride, total_bytes, w, lane);
+        wave_sync();
+        uint32_t u[16], mx = 0;
+        int wl = w;
+        asm volatile("" : "+s"(wl));                      // see records_encode
+        fields_unpack(reinterpret_cast<const uint16_t *>(pk) + lane * wl, u, wl);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int4 t;                                       // u - B: the low 32 bits are z whenever u <= 2B
+            t.x = (int)(u[4 * k + 0] - (uint32_t)bound);
+            t.y = (int)(u[4 * k + 1] - (uint32_t)bound);
+            t.z = (int)(u[4 * k + 2] - (uint32_t)bound);
+            t.w = (int)(u[4 * k + 3] - (uint32_t)bound);
+            mx = max(max(mx, max(u[4 * k + 0], u[4 * k + 1])), max(u[4 * k + 2], u[4 * k + 3]));
+            *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = t;
+        }
+        const bool bad = mx > two_b;
+        wave_sync();
+        if constexpr (COEF) {
+            double a[16];
+            {
+                int x[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) x[k] = stage[pad4(p * D + r + L * k)];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) a[k] = (double)x[k];
+            }
+            wave_sync();
+            TabPtr t = (TabPtr)tab;
+            asm volatile("" : "+s"(t));
+            fwd16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int4 o;
+                o.x = (int)fz_cent(a[4 * k + 0], m);
+                o.y = (int)fz_cent(a[4 * k + 1], m);
+                o.z = (int)fz_cent(a[4 * k + 2], m);
+                o.w = (int)fz_cent(a[4 * k + 3], m);
+                *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = o;
+            }
+            wave_sync();
+        }
+        const int4 o0 = *reinterpret_cast<const int4 *>(stage + pad4(4 * lane));
+        const int4 o1 = *reinterpret_cast<const int4 *>(stage + pad4(256 + 4 * lane));
+        const int4 o2 = *reinterpret_cast<const int4 *>(stage + pad4(512 + 4 * lane));
+        const int4 o3 = *reinterpret_cast<const int4 *>(stage + pad4(768 + 4 * lane));
+        wave_sync();
+        if (more) packed_to_lds(pk, raw, w, lane);        // waits for the prefetched loads (no store is younger)
+        chunk_store(out, task, total, lane, o0, o1, o2, o3);
+        const bool valid = task * kChunk + 16 * lane < total;
+        records_flag(status, walk.rec, bad && valid, FZ_VERDICT_ENCODING, lane);
+        walk.step();
+    };
+    size_t task = first;
+    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
+    iteration(task, std::false_type());
+}
+
+// the follow-up of both: a record whose status word is set gets all-zero output (bytes or rows), so what a launch leaves is a
+// function of its input alone.  Records are 8-byte multiples; a workgroup per record, striding.
+__global__ __launch_bounds__(256) void records_zero_failed(const int *status, size_t n, uint8_t *dst, size_t rec_bytes) {
+    for (size_t rec = blockIdx.x; rec < n; rec += gridDim.x) {
+        if (status[rec] == 0) continue;
+        fz_v2i *p = reinterpret_cast<fz_v2i *>(dst + rec * rec_bytes);
+        const fz_v2i zero = {0, 0};
+        for (size_t i = threadIdx.x; i < rec_bytes / 8; i += blockDim.x) p[i] = zero;
+    }
+}
+
+}  // namespace
+
+// compact byte encoding (fz_encode_records_async / fz_decode_records_async): d_status cleared, the records kernel over the batch,
+// then the zeroing of failed records.  Asynchronous and allocation-free: a graph capture records all three.  Verification keys (no
+// transform) take one instantiation.  The grid is capped at the kernel's OWN resident grid (fz_records_query_grid), as launch16f caps
+// the transforms at theirs: the FAST encode holds more registers than ntt_inv16 (3 workgroups per CU against 4), and a grid sized
+// for the transform would leave a quarter of its workgroups for a second round of the grid-stride walk.
+template <int LOGD, bool FAST, bool COEF>
+static void launch_records_k(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t total, unsigned rv, int w, int bound,
+                             int *d_status) {
+    const size_t tasks = (total + kChunk - 1) / kChunk, blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
+    const size_t cap = (size_t)ctx->grid_rec[(decode ? 1 : 0) + (COEF ? 0 : 2)];
+    const dim3 grid((unsigned)(blocks < cap ? blocks : cap)), block(64 * kWavesPerBlock);
+    if (decode)
+        hipLaunchKernelGGL((records_decode<LOGD, FAST, COEF>), grid, block, 0, ctx->stream, (const uint8_t *)src, (int32_t *)dst, total, rv,
+                           w, bound, d_status, (const double2 *)ctx->d_twB, (const FzTwA *)ctx->d_twAB, ctx->mod);
+    else
+        hipLaunchKernelGGL((records_encode<LOGD, FAST, COEF>), grid, block, 0, ctx->stream, (const int32_t *)src, (uint8_t *)dst, total, rv,
+                           w, bound, d_status, (const double2 *)ctx->d_itwB, (const FzTwA *)ctx->d_twAB + 1, ctx->mod);
+}
+
+// resident grids of the records kernels this context launches: [encode, decode] x [coefficient kinds, keys]
+template <int LOGD, bool FAST>
+static int query_records(fz_ctx *ctx) {
+    const void *k[4] = {(const void *)records_encode<LOGD, FAST, true>, (const void *)records_decode<LOGD, FAST, true>,
+                        (const void *)records_encode<8, true, false>, (const void *)records_decode<8, true, false>};
+    int rc = FZ_OK;
+    for (int i = 0; i < 4 && rc == FZ_OK; ++i) rc = fz_resident_grid(ctx, k[i], 64 * kWavesPerBlock, "occupancy query (records)", &ctx->grid_rec[i]);
+    return rc;
+}
+
+int fz_records_query_grid(fz_ctx *ctx) {
+    return fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) { return query_records<logd(), fast()>(ctx); });
+}
+
+int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
+                      int *d_status) {
+    const unsigned rv = (unsigned)rows * (unsigned)ctx->degree;
+    const size_t total = n * rv;
+    int rc = fz_check_hip(hipMemsetAsync(d_status, 0, n * sizeof(int), ctx->stream), "records status clear");
+    if (rc != FZ_OK) return rc;
+    const int b = (int)bound;
+    if (!coef) launch_records_k<8, true, false>(ctx, decode, src, dst, total, rv, w, b, d_status);
+    else
+        rc = fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
+            launch_records_k<logd(), fast(), true>(ctx, decode, src, dst, total, rv, w, b, d_status);
+            return FZ_OK;
+        });
+    if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "records launch");
+    if (rc != FZ_OK) return rc;
+    const size_t rec_bytes = decode ? (size_t)rv * sizeof(int32_t) : (size_t)rv / 8 * (size_t)w;
+    const size_t zcap = (size_t)ctx->num_cu * 4;
+    hipLaunchKernelGGL(records_zero_failed, dim3((unsigned)(n < zcap ? n : zcap)), dim3(256), 0, ctx->stream, (const int *)d_status, n,
+                       (uint8_t *)dst, rec_bytes);
+    return fz_check_hip(hipGetLastError(), "records zeroing launch");
+}

@@ -7,7 +7,7 @@ with c ~ a*w/q, so |t| ~ |c| * delta: exact while |a| <= 2^38, but once |c| * de
 the fixtures' operands are odd where they are meant to be large (a sum of 2^k equal int32 values is even, and an even t
 stays exact up to 2^54), and the tables hold odd twiddles next to q - 1.
 
-The inverse kernels keep their operands under 2^38 by folding at fixed places (csrc/fz_ntt.hip):
+The inverse kernels keep their operands under 2^38 by folding at fixed places (csrc/fz_ntt_dev.h):
 - 16-per-lane (inv16_passes: ntt_inv16, ntt_jobs16, polymul16): after the contiguous pass (GS stages of distance 1 ..
   2^(SB-1), SB = log2(D) - 4) the value at positions 0 mod 16 is folded when 31 + SB + 4 > 38, i.e. at degree 256 only;
 - radix-4 (inv4_passes_n: ntt_inv4, ntt_jobs4, polymul_fused, verify_fused): after pass 0 (distances 1 and 2) the value at
@@ -163,7 +163,7 @@ def few_rows(q, n):
 
 # ---- the model --------------------------------------------------------------------------------------------------------------
 def fold_sites(family, logd, fast):
-    """[(after GS stage index, position modulus)]: where the inverse schedule folds (csrc/fz_ntt.hip's conditions verbatim);
+    """[(after GS stage index, position modulus)]: where the inverse schedule folds (csrc/fz_ntt_dev.h's conditions verbatim);
     stage index i is the GS stage of distance 2^i.  family: "16" (inv16_passes), "4" (inv4_passes_n), "small" / "big" (no
     4-op multiply: ntt_big folds every sum into the 6-op form's range, ntt_small needs none below 2^35)"""
     if family == "16" and 5 <= logd <= 8:

@@ -6,14 +6,11 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "fusion-cryptography_amd", "csrc")
 G = os.path.join(os.path.dirname(__file__), "golden")
 
 # kind -> secpar -> (rows, B, w, record bytes), the table of INTEGRATION.md section G
@@ -176,32 +173,15 @@ def test_spec_decode_is_the_forward_transform_of_the_fields():
     assert all(py_cent(int(v), q) == int(v) for v in back.ravel()[:64])
 
 
-def test_record_kernels_compile_without_spills(tmp_path_factory):
+def test_record_kernels_compile_without_spills():
     """records_encode / records_decode / records_zero_failed: degrees 64 and 256 x both multiplies for the coefficient kinds, one
     instantiation each for keys; no spill, no scratch, and no more LDS than the transforms (lds16_doubles)"""
-    out = tmp_path_factory.mktemp("isa") / "fz_ntt.s"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           os.path.join(CSRC, "fz_ntt.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = {}
-    for entry in text[text.index("amdhsa.kernels:"):].split("\n  - ")[1:]:          # one metadata entry per kernel
-        name = re.search(r"\.name:\s+(\S+)", entry)                              # (amdhsa.version's list has none)
-        if not name or not re.search(r"records_|ntt_inv16|ntt_fwd16", name.group(1)):
-            continue
-        name = name.group(1)
-        f = dict(re.findall(r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)",
-                            entry))
-        f = {k: int(v) for k, v in f.items()}
-        f["lds"] = f.pop("group_segment_fixed_size")
-        meta[name] = f
-    records = {k: v for k, v in meta.items() if "records_" in k}
+    from _isa import asm, metadata
+    records = metadata(asm("fz_records"), "records_")
     assert len([k for k in records if "records_encode" in k]) == 5, sorted(records)
     assert len([k for k in records if "records_decode" in k]) == 5, sorted(records)
     assert len([k for k in records if "records_zero_failed" in k]) == 1, sorted(records)
-    lds = {k: v["lds"] for k, v in meta.items() if "ntt_inv16" in k or "ntt_fwd16" in k}
+    lds = {k: v["lds"] for k, v in metadata(asm("fz_transforms"), "ntt_inv16|ntt_fwd16").items()}
     for name, f in records.items():
         assert f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0 and f["private_segment_fixed_size"] == 0, (name, f)
         logd = re.search(r"records_(?:encode|decode)ILi(\d)E", name)

@@ -9,38 +9,29 @@ breaks it fails the CPU suite instead of producing a rare wrong verdict:
   * the arrival counter is bumped only after that barrier,
   * the default build contains no `buffer_wbl2` / `buffer_inv` (the fence-free form is what is being measured), the
     FZ_VERIFY_ORDERED instantiation contains both."""
-import os
+import collections
 import re
-import subprocess
 
-import pytest
+from _isa import TRANSFORM_UNITS, asm, bodies, family, metadata
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "fusion-cryptography_amd", "csrc")
-
-
-@pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "fz_ntt.s"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           os.path.join(CSRC, "fz_ntt.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
-    return open(out).read()
+# kernels per family: the host dispatch instantiates one for every (degree, multiply form, shape) it can launch and no other
+KERNELS = {"ntt_fwd16": 8, "ntt_inv16": 8, "ntt_fwd4": 20, "ntt_inv4": 20, "ntt_jobs4": 60, "ntt_jobs16": 12, "ntt_jobs16_keep": 24,
+           "ntt_small": 8, "ntt_big": 2, "polymul_fused": 4, "polymul16": 8, "records_encode": 5, "records_decode": 5,
+           "records_zero_failed": 1, "keygen_fused": 8, "keygen_bcast_fused": 4, "verify_fused": 32, "diag_*": 3}
 
 
-def bodies(asm, needle):
-    """{mangled name: [instructions]} of every kernel whose name contains `needle`"""
-    out = {}
-    for m in re.finditer(r"^(_ZN\S*" + needle + r"\S*):\s*;.*?$(.*?)s_endpgm", asm, re.S | re.M):
-        ins = [ln.strip() for ln in m.group(2).splitlines() if ln.startswith("\t") and not ln.strip().startswith((".", ";"))]
-        out[m.group(1)] = ins
-    return out
+def test_the_units_hold_the_kernels_of_every_family_and_no_other():
+    got = collections.Counter()
+    for unit in TRANSFORM_UNITS:
+        for name in metadata(asm(unit)):
+            f = family(name)
+            got["diag_*" if f.startswith("diag_") else f] += 1
+    assert dict(got) == KERNELS
+    assert sum(got.values()) == 232
 
 
-def test_verify_fused_orders_its_adds_before_the_arrival(asm):
-    ks = bodies(asm, "verify_fused")
+def test_verify_fused_orders_its_adds_before_the_arrival():
+    ks = bodies(asm("fz_transforms"), "verify_fused")
     # degree 64 / 256 x general / pseudo-Mersenne multiply x int32 / int64 rows x ordered / not x integer / fp64 accumulation of
     # A * sigma (round 3 also carried one / two row groups per iteration x twiddles as pairs / w alone: 128 instantiations)
     assert len(ks) == 32, sorted(ks)
@@ -58,22 +49,13 @@ def test_verify_fused_orders_its_adds_before_the_arrival(asm):
         assert bool(fences) == ordered, (name, fences)
 
 
-def test_aggregate_onepass_instantiations_do_not_spill_and_add_with_returning_atomics(tmp_path_factory):
+def test_aggregate_onepass_instantiations_do_not_spill_and_add_with_returning_atomics():
     """aggregate_onepass<8, RAG, SIGN, AR>: the nine instantiations the launcher can pick (rows per column block 4 / 3 / 2 x plain /
     ragged / fused signing) keep their state in registers -- no scratch (a spill in the signer loop would double the launch) --
     and every cross-workgroup sum is added with a RETURNING 64-bit atomic (the arrival count travels in the word the add returns),
     paired with the one non-returning add that re-arms the word"""
-    out = tmp_path_factory.mktemp("isa") / "fz_pointwise.s"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           os.path.join(CSRC, "fz_pointwise.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = {}
-    for m in re.finditer(r"\.name:\s+(\S*aggregate_onepass\S*)\n(.*?)\.wavefront_size", text, re.S):
-        f = dict(re.findall(r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", m.group(2)))
-        meta[m.group(1)] = {k: int(v) for k, v in f.items()}
+    text = asm("fz_pointwise")
+    meta = metadata(text, "aggregate_onepass")
     assert len(meta) == 9, sorted(meta)
     for name, f in meta.items():
         assert f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0 and f["private_segment_fixed_size"] == 0, (name, f)

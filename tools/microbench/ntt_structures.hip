@@ -10,21 +10,14 @@
 // for the whole chip when vector issue and LDS are all that count.  Each workgroup also reads the shader clock (s_memtime)
 // against the 100 MHz reference (s_memrealtime): the chip does not hold its 2.4 GHz under this load.
 //
-// It compiles the library's own kernel source into this translation unit: inv4_passes_n IS the shipped radix-4 code; the
+// It compiles the library's own device building blocks into this translation unit: inv4_passes_n IS the shipped radix-4 code; the
 // 16-per-lane loop body is the shipped ntt_inv16's, between its load and its store.   usage: ntt_structures [R=200]
-#include "../../fusion-cryptography_amd/csrc/fz_ntt.hip"
+#include "../../fusion-cryptography_amd/csrc/fz_ntt_dev.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-
-int fz_set_error(int code, const char *, ...) { return code; }
-int fz_check_hip(hipError_t e, const char *what) {
-    if (e != hipSuccess) { printf("HIP error in %s: %s\n", what, hipGetErrorString(e)); return FZ_E_HIP; }
-    return FZ_OK;
-}
-int fz_verify_scratch(fz_ctx *, size_t, size_t, double **, int **) { return FZ_E_UNSUPPORTED; }
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 

@@ -1,4 +1,5 @@
-"""Index-level model of the 16-coefficients-per-lane NTT kernels (csrc/fz_ntt.hip).
+"""Index-level model of the 16-coefficients-per-lane NTT kernels (csrc/fz_ntt_dev.h: fwd16_passes / inv16_passes;
+the kernels around them are in csrc/fz_ntt.hip).
 
 Pure-Python emulation of the data movement and twiddle indexing of the two-pass kernels
 (strided pass with wave-uniform twiddles / LDS transpose / contiguous pass with per-lane

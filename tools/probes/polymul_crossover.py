@@ -1,6 +1,6 @@
 """fz_poly_mul (algebra/ntt.py:380-484) in its two fused forms -- the radix-4 kernel (polymul_fused, FZ_POLYMUL_FORM=1) and the one on
 the 16-per-lane transforms (polymul16, FZ_POLYMUL_FORM=2) -- over batch sizes, on cold operands (sets rotate through 2.25 GiB pools),
-degrees 256 and 64: where the second overtakes the first is kPolymul16MinCoefs in csrc/fz_ntt.hip.  HIP events on the kernels' stream.
+degrees 256 and 64: where the second overtakes the first is kPolymul16MinRows256 in csrc/fz_polymul.hip.  HIP events on the kernels' stream.
 Output: profiles/r06_polymul_crossover.txt"""
 import os
 import sys
