@@ -367,6 +367,7 @@ static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint
     if (rc == FZ_OK) rc = fz_check_hip(hipMalloc((void **)&c->d_verdict, 64 * sizeof(int)), "verdict alloc");
     c->verdict_cap = 64;
     if (rc == FZ_OK && !ring_only) rc = fz_ntt_query_grid(c);
+    if (rc == FZ_OK && !ring_only) rc = fz_aggregate_encoded_query_grid(c);
     free(tw); free(itw); free(twB); free(itwB);
     if (rc != FZ_OK) { fz_ctx_destroy(c); return rc; }
     fz_registry_add(c);
@@ -1270,6 +1271,30 @@ int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int r
     if (n == 0) return FZ_OK;
     FZ_DEV(ctx);
     return fz_launch_records(ctx, true, d_bytes, d_rows, n, rows, coef != 0, w, bound, d_status);
+}
+
+int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status) {
+    int w = 0;
+    FZ_TRY(records_args(ctx, d_bytes, d_bytes, n, rows, bound, d_status, &w));
+    if (n == 0) return FZ_OK;
+    FZ_DEV(ctx);
+    return fz_launch_check_records(ctx, d_bytes, n, rows, w, bound, d_status);
+}
+
+int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip, size_t N, int l,
+                               int64_t bound, int64_t *d_partial, int32_t *d_out) {
+    int w = 0;
+    FZ_REQUIRE(N == 0 || d_alpha_hat, "NULL argument");
+    FZ_REQUIRE((((uintptr_t)d_alpha_hat | (uintptr_t)d_out) & 15) == 0, "alpha_hat and the aggregate must be 16-byte aligned");
+    FZ_TRY(records_args(ctx, d_bytes, d_partial, N, l, bound, (const int *)d_alpha_hat, &w));
+    if (N == 0) return FZ_OK;
+    if (((size_t)l * ctx->degree / 8 * (size_t)w) % 16 != 0)
+        return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: the aggregation from bytes needs a multiple of 16",
+                            (size_t)l * ctx->degree / 8 * (size_t)w);
+    if (N >= ((size_t)1 << 22))
+        return fz_set_error(FZ_E_UNSUPPORTED, "N=%zu too large for exact fp64 accumulation (< 2^22)", N);
+    FZ_DEV(ctx);
+    return fz_launch_aggregate_encoded(ctx, d_bytes, d_alpha_hat, d_skip, N, l, w, bound, d_partial, d_out);
 }
 
 int fz_verify_partials_batch_async(fz_ctx *ctx, const int32_t *d_A, const int64_t *d_partial, size_t partial_stride,

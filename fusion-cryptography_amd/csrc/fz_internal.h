@@ -68,6 +68,7 @@ struct fz_ctx {
     int grid_pm;                 // resident grid of the fused product kernel (0 = not queried yet)
     int grid_pm16;               // ... of its 16-per-lane form
     int grid_rec[4];             // ... of the byte-encoding kernels: [encode, decode] x [coefficient kinds, keys] (degree 64 / 256)
+    int grid_aggenc, grid_check; // ... of aggregate_encoded and encoded_check (fz_aggregate_encoded.hip; degree 64 / 256)
     int knob_ntt_rows;           // FZ_NTT_ROWS = 1 | 2 | 4: row groups per wave of the radix-4 kernels (0 = by batch size)
     // per-dispatch timing of the NTT kernels (fz_profile_begin/end): event pairs bound to the
     // dispatch itself via hipExtLaunchKernelGGL, i.e. kernel begin -> kernel end on its own stream
@@ -224,6 +225,15 @@ bool fz_polymul16_ok(const fz_ctx *ctx, const int32_t *f, const int32_t *g, cons
 int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
                       int *d_status);
 int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_rec (fz_ntt_query_grid calls it)
+
+// the byte encoding's consumers without rows (fz_aggregate_encoded.hip; degree 64 / 256): the range check of a byte stream alone
+// (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from
+// their bytes: d_partial [l][degree] int64 zeroed, then sum_i cent(NTT(z_i) (.) alpha_hat_i) over the signers with skip[i] == 0
+// (skip NULL: all), d_out = cent(d_partial) when not NULL.  Records of the aggregation are multiples of 16 bytes.
+int fz_aggregate_encoded_query_grid(fz_ctx *ctx);                  // ctx->grid_aggenc, ctx->grid_check (context creation)
+int fz_launch_check_records(fz_ctx *ctx, const uint8_t *bytes, size_t n, int rows, int w, int64_t bound, int *d_status);
+int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, int l, int w,
+                                int64_t bound, int64_t *d_partial, int32_t *d_out);
 
 // fused keygen and verification (fz_scheme_fused.hip)
 int fz_launch_keygen_fused(fz_ctx *ctx, const int32_t *A, const int32_t *coef, int32_t *sk_hat, int32_t *vk, size_t segments,

@@ -590,6 +590,36 @@ def from_bytes(params: Params, kind: str, data: bytes):
     return vk_to_object(params, rows[0]) if kind == "vk" else signature_to_object(params, rows[0])
 
 
+def aggregate_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
+                         blobs: List[bytes]) -> Signature:
+    """NOT in the reference: aggregate() of signatures given as their compact bytes (one "signature" record of to_bytes
+    each), without ever expanding them -- the Signature that aggregate(params, keys, messages, [from_bytes(params,
+    "signature", b) for b in blobs]) returns (BatchScheme.aggregate_encoded: one fused pass over the bytes).  Raises
+    ValueError for unequal numbers of keys, messages and blobs, for a blob of the wrong length, and for a record that is not
+    canonical (with the index of the first one and the reason).  The target equation of a signature is NOT checked, as
+    aggregate() does not check it either: verify() the result."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import BatchScheme, encoded_size, vk_from_object
+    if not (len(keys) == len(messages) == len(blobs)):
+        raise ValueError(f"{len(keys)} keys, {len(messages)} messages, {len(blobs)} records")
+    size = encoded_size(params, "signature")
+    for i, b in enumerate(blobs):
+        if len(b) != size:
+            raise ValueError(f"record {i}: a 'signature' record is {size} bytes, not {len(b)}")
+    if not blobs:
+        raise ValueError("no records to aggregate")
+    vk = np.stack([vk_from_object(params, k) for k in keys])
+    bs = BatchScheme(params)
+    try:
+        out, codes = bs.aggregate_encoded(vk, list(messages), b"".join(bytes(b) for b in blobs))
+    finally:
+        bs.close()
+    bad = np.flatnonzero(codes)
+    if bad.size:
+        raise ValueError(f"record {int(bad[0])}: {ENCODING_REASONS[int(codes[bad[0]])]}")
+    return Signature(signature_hat=_column(params, out))
+
+
 _ORIGINALS.update({name: globals()[name] for name in (
     "decode_bytes_to_polynomial_coefficients", "hash_ch", "parse_challenge", "transform", "sample_coefficient_matrix", "hash_ag",
     "sample_polynomial_coefficient_representation")})

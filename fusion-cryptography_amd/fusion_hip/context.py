@@ -410,6 +410,17 @@ class Context:
         check(self._lib, self._lib.fz_decode_records_async(self._h, c_void_p(d_bytes), n, rows, 1 if coef else 0, bound,
                                                            c_void_p(d_rows), c_void_p(d_status)))
 
+    def check_records_async_dev(self, d_bytes, n, rows, bound, d_status):
+        """decode's range check alone: codes (0, 6) to d_status [n]; no rows are written (asynchronous)"""
+        check(self._lib, self._lib.fz_check_records_async(self._h, c_void_p(d_bytes), n, rows, bound, c_void_p(d_status)))
+
+    def aggregate_encoded_async_dev(self, d_bytes, d_alpha, d_skip, N, l, bound, d_partial, d_out):
+        """the aggregate of N signature records straight from their bytes: d_partial [l][d] int64 = the sum over the signers
+        with d_skip[i] == 0 (d_skip 0 / None: all) of cent(NTT(z_i) (.) alpha_hat_i), d_out [l][d] int32 = cent(d_partial)
+        when not 0 / None; fields are not range checked (check_records_async_dev first) (asynchronous)"""
+        check(self._lib, self._lib.fz_aggregate_encoded_async(self._h, c_void_p(d_bytes), c_void_p(d_alpha), c_void_p(d_skip or None),
+                                                              N, l, bound, c_void_p(d_partial), c_void_p(d_out or None)))
+
     def reduce_i64_dev(self, d_in, d_out, count):
         check(self._lib, self._lib.fz_reduce_i64(self._h, c_void_p(d_in), c_void_p(d_out), count))
 

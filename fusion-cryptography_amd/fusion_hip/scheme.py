@@ -52,6 +52,24 @@ def encoded_size(params, kind):
     return _encoding(params, kind)[4]
 
 
+def _records_input(kind, data, rb):
+    """the byte input of decode / aggregate_encoded (bytes, bytearray, memoryview, a uint8 numpy array or a uint8 DeviceArray)
+    -> (a uint8 numpy array or the DeviceArray, N); FusionHipError(FZ_E_BADARG) unless it is N whole records of rb bytes"""
+    if isinstance(data, DeviceArray):
+        if data.dtype != np.uint8:
+            raise FusionHipError(FZ_E_BADARG, f"device array of {data.dtype}: uint8 expected")
+        nbytes = int(np.prod(data.shape))
+    else:
+        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(data)
+        if data.dtype != np.uint8:
+            raise FusionHipError(FZ_E_BADARG, f"array of {data.dtype}: uint8 expected")
+        nbytes = data.size
+    if nbytes % rb:
+        raise FusionHipError(FZ_E_BADARG, f"{nbytes} bytes are not a whole number of {rb}-byte {kind!r} records")
+    return data, nbytes // rb
+
+
 def screened_alpha_coefficients(P, L, R, pre, c_hat, valid=None, threads=None, order=None):
     """hash_ag without the transforms (fusion.py:632-652) for ONE aggregate of the signers with valid[i] set: sort them by
     str(vk) (fusion.py:661-663, :693), the one serial SHAKE-256 over the sorted list, decode.
@@ -513,19 +531,7 @@ class BatchScheme:
         (ENCODING_REASONS) when record i is not canonical (a field above 2B), and its rows are then zero.  A length that is not
         a whole number of records raises FusionHipError(FZ_E_BADARG)."""
         nrows, coef, bound, w, rb = _encoding(self.params, kind)
-        if isinstance(data, DeviceArray):
-            if data.dtype != np.uint8:
-                raise FusionHipError(FZ_E_BADARG, f"device array of {data.dtype}: uint8 expected")
-            nbytes = int(np.prod(data.shape))
-        else:
-            data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
-                np.ascontiguousarray(data)
-            if data.dtype != np.uint8:
-                raise FusionHipError(FZ_E_BADARG, f"array of {data.dtype}: uint8 expected")
-            nbytes = data.size
-        if nbytes % rb:
-            raise FusionHipError(FZ_E_BADARG, f"{nbytes} bytes are not a whole number of {rb}-byte {kind!r} records")
-        n = nbytes // rb
+        data, n = _records_input(kind, data, rb)
         if n == 0:
             empty = np.zeros((0, nrows, self.d), dtype=np.int32)
             return (DeviceArray.from_numpy(self.ctx, empty) if device else empty), np.zeros(0, dtype=np.int32)
@@ -541,6 +547,54 @@ class BatchScheme:
             return dR.numpy(), codes
         finally:
             for b, o in ((dB, own), (dR, True), (dV, True)):
+                if o and b is not None:
+                    b.free()
+
+    def aggregate_encoded(self, vk, messages, data):
+        """aggregate() straight from the signatures' compact bytes (`data`: N "signature" records in every form decode
+        takes): -> (aggregate [l][d] int32, or None when no record is canonical; codes int32 [N]).  codes[i] is 0, or 6
+        (ENCODING_REASONS) when record i is not canonical (a field above 2B); the aggregate is bit for bit
+        aggregate(vk[ok], messages[ok], decode("signature", data)[0][ok]) over the records with code 0 -- hash_ag runs over
+        those signers only, as aggregate_screened does.  The bytes are uploaded once, range-checked (beside the challenge pass
+        and the key sort), and one fused pass unpacks, transforms, multiplies and accumulates them: the int32 rows of the
+        signatures (2.46 times the bytes at secpar 256) never exist on the device.
+        What this call does NOT do: a canonical record is within the norm bound of ONE signature, but its target equation
+        A (.) sig_i == vkL_i (.) c_i + vkR_i is not checked.  An aggregator of untrusted input verifies its own aggregate
+        (verify); when that fails it falls back to decode + aggregate_screened, which names the signer.
+        A length that is not N whole records, or numbers of keys / messages other than N, raise FusionHipError(FZ_E_BADARG)
+        before the device is touched."""
+        nrows, _, bound, _, rb = _encoding(self.params, "signature")
+        data, n = _records_input("signature", data, rb)
+        nk = vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+        if not (nk == len(messages) == n):
+            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
+        if n == 0:
+            return None, np.zeros(0, dtype=np.int32)
+        own = not isinstance(data, DeviceArray)
+        dB = DeviceArray.from_numpy(self.ctx, data.reshape(n, rb)) if own else data
+        dV = dAl = dP = dO = None
+        try:
+            dV = DeviceArray(self.ctx, (n,))
+            self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
+            vk, L, R = self._split_vk(vk)
+            order_f = self._sort_async(L, R)                # beside the check and the challenge pipeline
+            try:
+                dC, c_hat, pre = self._challenges_both(vk, messages)
+                dC.free()                                   # hash_ag reads the host copy; nothing here needs c_hat on the device
+            finally:
+                order = order_f.result()
+            codes = dV.numpy()
+            valid = codes == 0
+            if not valid.any():
+                return None, codes
+            _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads, order)
+            dAl = DeviceArray.from_numpy(self.ctx, alpha)
+            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
+            dP, dO = DeviceArray(self.ctx, (self.l, self.d), np.int64), DeviceArray(self.ctx, (self.l, self.d))
+            self.ctx.aggregate_encoded_async_dev(dB.ptr, dAl.ptr, dV.ptr, n, self.l, bound, dP.ptr, dO.ptr)
+            return dO.numpy(), codes
+        finally:
+            for b, o in ((dB, own), (dV, True), (dAl, True), (dP, True), (dO, True)):
                 if o and b is not None:
                     b.free()
 

@@ -335,6 +335,22 @@ FZ_API int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n,
 FZ_API int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int coef, int64_t bound,
                                    int32_t *d_rows, int *d_status);
 
+/* the range check of fz_decode_records_async alone (no transform, no rows): status per record 0 or FZ_VERDICT_ENCODING (a field
+ * > 2 * bound); nothing else is written.  Same arguments and rules as fz_decode_records_async, for either kind of record. */
+FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status);
+
+/* aggregation straight from the bytes of N signature records of l rows (no int32 row of a signature reaches memory):
+ * d_partial [l][degree] int64 = sum over signers i with d_skip[i] == 0 (d_skip may be NULL: none skipped) of
+ * NTT(z_i) (.) alpha_hat_i, every product reduced mod q before it is added (|value| <= N*(q-1)/2), z_i the fields of
+ * record i minus bound; d_out [l][degree] int32 = cent(d_partial) when not NULL (fz_reduce_i64's step).  The call overwrites
+ * both.  d_alpha_hat [N][degree] takes any int32 value, as fz_aggregate_core's does.  The fields of a record are NOT range
+ * checked here (a field above 2 * bound enters as the low 32 bits of field - bound): run fz_check_records_async first and pass
+ * its status words as d_skip -- a skipped record's bytes are never read.  Rules of fz_decode_records_async (degree 64 or 256,
+ * 1 <= bound <= (q-1)/2, l >= 1, 16-byte aligned pointers, N == 0 does nothing); FZ_E_UNSUPPORTED also for records that are
+ * no multiple of 16 bytes (degree 64 with l * w odd) and for N >= 2^22.  Asynchronous, allocation-free, capturable. */
+FZ_API int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
+                                      size_t N, int l, int64_t bound, int64_t *d_partial, int32_t *d_out);
+
 /* ---- the exchange step across GPUs: RCCL all-reduce of the int64 partial sums -------------------
  * aggregate() (fusion.py:670-676) and verify()'s target (:706-714) are sums over signers; with the signers sharded over
  * GPUs each rank holds exact int64 partials (fz_aggregate_partial*, fz_target_partial*, fz_aggregate_target_partial_batch)
