@@ -1532,6 +1532,9 @@ int fz_sample_secret_polys_dev(fz_ctx *ctx, const uint64_t *h_seeds, size_t N, i
     if (fz_capturing(ctx)) return fz_set_error(FZ_E_BADARG, "the sampler uploads the seeds: not during graph capture");
     const int64_t bound = std::max<int64_t>(0, std::min<int64_t>(modulus / 2, norm_bound));
     if (bound < 1 || bound >= (1ll << 32)) return fz_set_error(FZ_E_BADARG, "empty range for randrange()");
+    // a coefficient is stored as an int32: magnitudes run up to the bound, and from 2^31 on they would wrap silently
+    if (bound > INT32_MAX)
+        return fz_set_error(FZ_E_UNSUPPORTED, "sampler: a norm bound above 2^31 - 1 does not fit the int32 coefficients");
     if (weight_bound < degree)
         return fz_set_error(FZ_E_UNSUPPORTED, "device sampler: weight bound = degree only (no shuffle); use fz_sample_secret_polys");
     // the right half of a key is seeded with seed + 1: at seed = 2^64 - 1 that is 2^64, a THREE-word key for CPython's

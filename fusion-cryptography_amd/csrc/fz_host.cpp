@@ -744,6 +744,9 @@ int fz_sample_coefficients_state(uint64_t seed, int64_t modulus, int degree, int
     const int count = (int)std::max<int64_t>(0, std::min<int64_t>(degree, weight_bound));
     const int64_t bound = std::max<int64_t>(0, std::min<int64_t>(modulus / 2, norm_bound));
     if (count > 0 && (bound < 1 || bound >= (1ll << 32))) return fz_set_error(FZ_E_BADARG, "empty range for randrange()");
+    // a coefficient is stored as an int32: magnitudes run up to the bound, and from 2^31 on they would wrap silently
+    if (count > 0 && bound > INT32_MAX)
+        return fz_set_error(FZ_E_UNSUPPORTED, "sampler: a norm bound above 2^31 - 1 does not fit the int32 coefficients");
     for (int j = 0; j < degree; ++j) h_out[j] = 0;
     for (int j = 0; j < count; ++j) {
         const int64_t mag = 1 + (int64_t)rng.randbelow((uint32_t)bound);
@@ -763,6 +766,8 @@ int fz_sample_secret_polys(const uint64_t *h_seeds, size_t N, int64_t modulus, i
     for (size_t i = 0; i < N; ++i)      // seed + 1 must not wrap: CPython seeds 2^64 with a three-word key, not with 0
         if (h_seeds[i] == UINT64_MAX)
             return fz_set_error(FZ_E_UNSUPPORTED, "seed %zu is 2^64 - 1: seed + 1 needs a wider key than this sampler takes", i);
+    if (N && degree >= 1 && weight_bound >= 1 && std::min<int64_t>(modulus / 2, norm_bound) > INT32_MAX)      // (the workers' own code is lost below)
+        return fz_set_error(FZ_E_UNSUPPORTED, "sampler: a norm bound above 2^31 - 1 does not fit the int32 coefficients");
     std::atomic<int> bad(0);      // set by any worker thread
     parallel_for(2 * N, threads, [&](size_t i) {
         if (fz_sample_coefficients(h_seeds[i / 2] + (i & 1), modulus, degree, norm_bound, weight_bound,

@@ -460,7 +460,9 @@ FZ_API int fz_challenge_hat_msgs_dev(fz_ctx *ctx, const fz_scheme_params *P, con
  * CPython's MT19937 `random` exactly as the reference's samplers drive it (random.seed(int), randrange):
  * the same seed yields the same polynomial as algebra/polynomials.py:436-488.  Seeds are the non-negative integers below
  * 2^64 (fz_sample_secret_polys: below 2^64 - 1, because the right half uses seed + 1); callers map other Python seeds
- * themselves (random.seed(int) uses abs(seed); larger ones need more key words than these entries take). */
+ * themselves (random.seed(int) uses abs(seed); larger ones need more key words than these entries take).
+ * The coefficient samplers (host and device) take a bound min(modulus / 2, norm_bound) of at most 2^31 - 1: a coefficient is an
+ * int32 and magnitudes run up to the bound; a larger one is FZ_E_UNSUPPORTED. */
 FZ_API int fz_sample_ntt_values(uint64_t seed, int64_t modulus, int degree, int32_t *h_out);
 FZ_API int fz_sample_coefficients(uint64_t seed, int64_t modulus, int degree, int64_t norm_bound,
                                   int64_t weight_bound, int32_t *h_out);
@@ -474,7 +476,8 @@ FZ_API int fz_sample_secret_polys(const uint64_t *h_seeds, size_t N, int64_t mod
 /* The same on the DEVICE (csrc/fz_sample.hip): one lane per polynomial runs CPython's MT19937 exactly (init_by_array
  * seeding, getrandbits, rejection) and writes d_out [N][2][degree] in device memory -- what fz_keygen_core_bcast reads, so
  * the secret polynomials of keygen(params, seed) never exist on the host.  Supported: weight_bound >= degree (both parameter
- * sets: no shuffle), seeds < 2^64 - 1 (the right half is seeded with seed + 1, which must not wrap); else
+ * sets: no shuffle), seeds < 2^64 - 1 (the right half is seeded with seed + 1, which must not wrap), and polynomials that
+ * complete within 16 generations = 9984 outputs of their generator (the scheme's take about 830); else
  * FZ_E_UNSUPPORTED.  Synchronous (it reads back a completion flag). */
 FZ_API int fz_sample_secret_polys_dev(fz_ctx *ctx, const uint64_t *h_seeds, size_t N, int64_t modulus, int degree,
                                       int64_t norm_bound, int64_t weight_bound, int32_t *d_out);
