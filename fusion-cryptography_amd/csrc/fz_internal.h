@@ -8,6 +8,7 @@
 #include <mutex>
 #include <type_traits>
 #include "fz_arith.h"
+#include "../../include/fusion_hip.h"
 
 // Wave-uniform twiddles of the strided pass, passed BY VALUE so they live in the kernarg
 // segment and reach the kernel as scalar loads (SGPR operands of the fp64 multiplies).
@@ -41,6 +42,22 @@ struct FzProduced {
     unsigned rows;
 };
 
+// A device area of the context that is replaced by a larger one on demand: the pointer and its capacity in bytes.  Every
+// area follows ONE rule, fz_area_fit below.
+struct FzArea {
+    void *p;
+    size_t bytes;
+};
+enum {
+    FZ_A_SCRATCH, FZ_A_SCRATCH2,   // host-pointer entry points, int64 partial sums
+    FZ_A_VERDICT,                  // verdicts of fz_verify_with_target_batch, one int per aggregate
+    FZ_A_VPART, FZ_A_VSTATE,       // fused verification (fz_verify_scratch)
+    FZ_A_AGGACC,                   // one-pass aggregation (fz_agg_scratch)
+    FZ_A_CHAL_TAB,                 // weight table of the challenge decoder (fz_challenge.hip), built on first use
+    FZ_A_STAMP,                    // fz_diag_stamps_*
+    FZ_A_COUNT
+};
+
 struct fz_ctx {
     int device;
     int num_cu;
@@ -59,11 +76,7 @@ struct fz_ctx {
     int small_batch_rows;        // below this many rows the radix-4 (4 coefficients per lane) kernels run
     int force_kernel;            // 0 auto, 4 radix-4, 16 sixteen-per-lane (env FZ_NTT_KERNEL; tests and A/B runs)
     FzTwA twA, itwA;
-    // growable device scratch (host-pointer entry points, int64 partial sums)
-    void *d_scratch, *d_scratch2;
-    size_t scratch_bytes, scratch2_bytes;
-    int *d_verdict;              // [verdict_cap]
-    size_t verdict_cap;
+    FzArea area[FZ_A_COUNT];     // the growable device areas (fz_area_fit); fz_ctx_destroy releases every one
     int grid_fwd, grid_inv;      // resident-grid caps for the persistent NTT kernels
     int grid_pm;                 // resident grid of the fused product kernel (0 = not queried yet)
     int grid_pm16;               // ... of its 16-per-lane form
@@ -78,18 +91,14 @@ struct fz_ctx {
     int capturing;               // between fz_graph_begin and fz_graph_end: nothing may allocate or synchronise
     // fused verification: per-aggregate fp64 accumulators of `observed` [groups][degree] and state words
     // (arrival / failure counts); all zero between launches -- the kernel re-arms them itself
-    double *d_vpart;
-    int *d_vstate;
-    size_t vpart_doubles, vstate_groups;
+    // (areas FZ_A_VPART, FZ_A_VSTATE)
     int verify_dirty;            // a verify launch failed: accumulators / state words are re-zeroed before the next one
     // one-pass aggregation: per (aggregate, column block) accumulator words [tiles][tile_words] (running sum + arrival
     // count, see aggregate_onepass); all zero between launches (the last adder of a word re-arms it)
-    unsigned long long *d_aggacc;
-    size_t aggacc_tiles;
+    // (area FZ_A_AGGACC)
     int agg_dirty;
     uint32_t *d_mt_init;         // MT19937 state after init_genrand(19650218) (fz_sample_secret_polys_dev), lazily
-    uint32_t *d_chal_tab;        // weight table of the challenge decoder (fz_challenge.hip), built on first use
-    int chal_tab_ib, chal_tab_degree;
+    int chal_tab_ib, chal_tab_degree;   // what the table in FZ_A_CHAL_TAB was built for
     // Pinned, device-visible staging for the SMALL host inputs of the fused challenge kernel (message bytes + offsets, or the
     // digests): the kernel reads them in place over the host link (three coalesced requests per wave), so a call uploads
     // nothing and does not synchronise.  Two slots in turn; a slot's event is recorded after the launch that reads it and
@@ -132,8 +141,7 @@ struct fz_ctx {
     // fz_diag_stamps_*: device-side launch timestamps of the multi-job transform ({entry, exit} of the 100 MHz reference counter
     // per workgroup); launch k of the recording owns slots [stamp_first[k], stamp_first[k] + stamp_count[k])
     int stamp_on, stamp_n, stamp_launch_cap;
-    size_t stamp_used, stamp_wg_cap;
-    unsigned long long *d_stamp;
+    size_t stamp_used, stamp_wg_cap;     // (the slots are area FZ_A_STAMP)
     size_t *stamp_first;
     unsigned *stamp_count;
 };
@@ -174,11 +182,45 @@ struct fz_graph {
 // largest transform length: up to 256 the register / LDS schedules of fz_ntt_dev.h, beyond it one workgroup per polynomial through LDS
 constexpr int kFzMaxDegree = 4096;
 
-// error plumbing (fz_capi.hip)
+// error plumbing (fz_context.hip)
 int fz_set_error(int code, const char *fmt, ...);
 int fz_check_hip(hipError_t e, const char *what);
-int fz_scratch(fz_ctx *ctx, size_t bytes, void **out);
-int fz_scratch2(fz_ctx *ctx, size_t bytes, void **out);
+#define FZ_TRY(x) do { int rc_ = (x); if (rc_ != FZ_OK) return rc_; } while (0)
+#define FZ_HIP(x, what) FZ_TRY(fz_check_hip((x), what))
+#define FZ_REQUIRE(cond, ...) do { if (!(cond)) return fz_set_error(FZ_E_BADARG, __VA_ARGS__); } while (0)
+// Every entry point that touches the device makes the context's device current first: a process may hold contexts on
+// several GPUs (and other code -- torch -- may have changed the current device behind our back); kernels, scratch
+// allocations and events must land on ctx->device whatever stream the caller attached.
+#define FZ_DEV(ctx) FZ_HIP(hipSetDevice((ctx)->device), "hipSetDevice")
+
+// Is work on this context being recorded rather than executed?  Either the context opened a capture itself (fz_graph_begin) or
+// its stream was drawn into another context's capture by fz_event_wait on an event recorded there (the fork / join of a
+// two-stream capture): the runtime knows, so ask it -- nothing may allocate, copy to the host or synchronise in either case.
+static inline bool fz_capturing(fz_ctx *ctx) {
+    if (ctx->capturing) return true;
+    if (!ctx->stream) return false;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st == hipStreamCaptureStatusActive;
+}
+
+// The one rule of the growable areas (fz_context.hip).  fz_area_replace: refused with FZ_E_BADARG during capture, before any
+// runtime call (the open capture stays valid); otherwise the context's stream is drained (the area's previous users are
+// stream-ordered before this point), the old allocation goes to fz_retire, the area is marked empty and `capacity` bytes are
+// allocated -- a failure leaves the area empty, never dangling.  The contents are undefined.  fz_area_fit: a request that fits
+// makes no runtime call; one that does not replaces the area and sets *fresh.
+int fz_area_replace(fz_ctx *ctx, int which, size_t capacity);
+static inline int fz_area_fit(fz_ctx *ctx, int which, size_t need, size_t capacity, bool *fresh = nullptr) {
+    if (need <= ctx->area[which].bytes) return FZ_OK;
+    if (fresh) *fresh = true;
+    return fz_area_replace(ctx, which, capacity);
+}
+static inline int fz_scratch(fz_ctx *ctx, size_t bytes, void **out, int which = FZ_A_SCRATCH) {
+    FZ_TRY(fz_area_fit(ctx, which, bytes, bytes + bytes / 4 + 4096));
+    *out = ctx->area[which].p;
+    return FZ_OK;
+}
+int fz_verdict_area(fz_ctx *ctx, size_t groups, int **d_verdict);
 int fz_verify_scratch(fz_ctx *ctx, size_t groups, size_t doubles_per_group, double **part, int **state);
 int fz_agg_scratch(fz_ctx *ctx, size_t tiles, size_t tile_words, unsigned long long **acc);
 int fz_retire(fz_ctx *ctx, void *d_ptr, const char *what);       // hipFree, or keep until destroy when graphs were captured

@@ -487,7 +487,7 @@ def test_a_captured_aggregation_survives_later_scratch_growth(coracle):
     """a graph that holds a multi-slice aggregation and a multi-workgroup verification has the addresses of the
     context's accumulator scratch baked in; later, larger calls on the same context make that scratch grow.  The old
     allocations must stay valid (retired, not freed) and re-armed, so that replaying the graph afterwards still gives the
-    oracle's aggregate and verdict (fz_retire, csrc/fz_capi.hip)."""
+    oracle's aggregate and verdict (fz_retire, csrc/fz_context.hip)."""
     import fusion_hip
     P = O.PARAMS[256]
     q, d, l = P["q"], P["d"], P["rank"]

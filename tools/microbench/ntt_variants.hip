@@ -21,7 +21,7 @@
 #include <cstring>
 #include <vector>
 
-// the few symbols fz_ntt.hip expects from fz_capi.hip
+// the few symbols fz_ntt.hip expects from fz_context.hip
 int fz_set_error(int code, const char *, ...) { return code; }
 int fz_check_hip(hipError_t e, const char *what) {
     if (e != hipSuccess) { printf("HIP error in %s: %s\n", what, hipGetErrorString(e)); return FZ_E_HIP; }
