@@ -17,9 +17,10 @@
 //   * values are exact integers in fp64 with lazy accumulation (fz_arith.h): one multiply + add + sub per butterfly -- the 4-op
 //     pseudo-Mersenne multiply where the modulus admits it (FAST; one fold in the inverse keeps its operands below 2^38), else
 //     the 6-op FMA-Barrett form -- and one centring per output.
-//   * a resident grid strides over the chunks in a software pipeline: the next chunk's loads are issued before the current one is
-//     computed, the stores are the youngest operations, and a wave's last chunk is peeled off so that no run-time branch
-//     surrounds the prefetch (fwd16_run).
+//   * a resident grid strides over the chunks in a software pipeline: the next chunk is requested straight into LDS
+//     (global_load_lds_dwordx4, into the part of the wave's region the transpose has just left) half an iteration ahead, the wait
+//     for it leaves the iteration's stores outstanding, and a wave's last chunk is peeled off so that no run-time branch
+//     surrounds the request (fwd16_run).
 // 4 per lane (radix-4 in place, degrees 64 and 256, small batches): ntt_fwd4 / ntt_inv4, one wave-task per wave, no loop.
 // ntt_jobs4 / ntt_jobs16 / ntt_jobs16_keep serve a table of jobs with the same wave-tasks in ONE dispatch (fz_ntt_multi).
 // D <= 16: a thread per polynomial (ntt_small); D = 512 .. 4096: a workgroup per polynomial through LDS (ntt_big).

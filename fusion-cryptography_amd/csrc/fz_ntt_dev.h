@@ -5,6 +5,7 @@
 #define FZ_NTT_DEV_H
 
 #include "fz_internal.h"
+#include <utility>
 
 namespace {
 typedef int fz_v4i __attribute__((ext_vector_type(4)));
@@ -83,6 +84,42 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// The same for the stretch of an iteration in which a direct-to-LDS chunk (chunk_load_lds) is in flight: a release at workgroup
+// scope would wait for that chunk (it writes LDS), which is the one thing the stretch exists not to do.  Wavefront scope still
+// keeps the compiler from moving LDS accesses across; a wave's DS instructions execute in order, and the data dependences on
+// the reads bring their own waits.
+__device__ __forceinline__ void wave_sync_inflight() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A WHOLE chunk straight into LDS: four global_load_lds_dwordx4 (1 KiB per wave instruction, lane i's 16 bytes at LDS base + 16 i;
+// the instruction offset advances the global and the LDS address alike), same scalar base, lane offset and streaming policy as
+// chunk_load.  The image at `land` is the chunk as it lies in memory: 4 KiB, no padding.  The chunk costs no register while in
+// flight and no ds_write afterwards; the compiler does not follow it into LDS, so the reader waits itself (chunk_landed).
+constexpr int kLandOff = kStageWords;                // word offset of the landing area in a wave's region: behind the staging image
+__device__ __forceinline__ void chunk_load_lds(const int32_t *in, size_t task, int lane, int32_t *land) {
+    typedef const __attribute__((address_space(1))) void *gptr;
+    typedef __attribute__((address_space(3))) void *lptr;
+    const gptr g = (gptr)(in + task * kChunk + 4 * lane);
+    const lptr l = (lptr)land;
+    __builtin_amdgcn_global_load_lds(g, l, 16, 0, 2);         // aux 2: nt
+    __builtin_amdgcn_global_load_lds(g, l, 16, 1024, 2);
+    __builtin_amdgcn_global_load_lds(g, l, 16, 2048, 2);
+    __builtin_amdgcn_global_load_lds(g, l, 16, 3072, 2);
+}
+
+// wait until a chunk_load_lds has landed that was followed by exactly YOUNGER vector memory operations (vmcnt counts loads and
+// stores in order of issue: s_waitcnt vmcnt(YOUNGER), the other counters left alone)
+template <int YOUNGER>
+__device__ __forceinline__ void chunk_landed() {
+    static_assert(YOUNGER >= 0 && YOUNGER < 16, "low four bits of vmcnt");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0x0F70 | YOUNGER);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 constexpr int kWavesPerBlock = 4;
 
 // Streaming (non-temporal) stores for outputs the kernel never reads back.  A normal store allocates the line
@@ -102,6 +139,27 @@ __device__ __forceinline__ void plain_store4(int32_t *p, const int4 &v) {
 
 // the task's 4 coalesced 16-byte stores (same scalar split as chunk_load: only a ragged last chunk predicates its lanes);
 // PLAIN: normal instead of streaming stores (ntt_jobs16_keep)
+// the stores of a chunk known to be whole: exactly four vector memory operations, and global ones whatever the compiler knows of
+// the pointer (the job tables of at most eight entries hand it over as a generic one: a flat store counts in lgkmcnt as well)
+template <bool PLAIN = false>
+__device__ __forceinline__ void chunk_store_whole(int32_t *out, size_t task, int lane, const int4 &o0, const int4 &o1, const int4 &o2,
+                                                  const int4 &o3) {
+    typedef __attribute__((address_space(1))) fz_v4i *gptr;
+    const gptr b = (gptr)(out + task * kChunk + 4 * lane);
+    const fz_v4i t0 = {o0.x, o0.y, o0.z, o0.w}, t1 = {o1.x, o1.y, o1.z, o1.w}, t2 = {o2.x, o2.y, o2.z, o2.w}, t3 = {o3.x, o3.y, o3.z, o3.w};
+    if constexpr (PLAIN) {
+        b[0] = t0;
+        b[64] = t1;
+        b[128] = t2;
+        b[192] = t3;
+    } else {
+        __builtin_nontemporal_store(t0, b);
+        __builtin_nontemporal_store(t1, b + 64);
+        __builtin_nontemporal_store(t2, b + 128);
+        __builtin_nontemporal_store(t3, b + 192);
+    }
+}
+
 template <bool PLAIN = false>
 __device__ __forceinline__ void chunk_store(int32_t *out, size_t task, size_t total, int lane, const int4 &o0, const int4 &o1,
                                             const int4 &o2, const int4 &o3) {
@@ -142,13 +200,35 @@ template <int LOGD> constexpr int lds16_doubles() {
     return kWavesPerBlock * G::PPW * G::PS + 2 * G::NE * G::L;
 }
 
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>), in order
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(const F &f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>()), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(const F &f) { static_for_seq(f, std::make_integer_sequence<int, N>()); }
+
+// The contiguous pass's per-lane twiddle pairs in the order the butterflies use them, cut into groups of at most four pairs
+// of ONE stage (16 registers): stage ls of SB has 16 >> (SB - ls) pairs in the forward direction (FWD), 8 >> ls in the inverse.
+template <int SB, bool FWD>
+struct TwGroups {
+    static constexpr int kPairs = 4;
+    static constexpr int pairs(int ls) { return FWD ? 16 >> (SB - ls) : 8 >> ls; }
+    static constexpr int groups_of(int ls) { return (pairs(ls) + kPairs - 1) / kPairs; }
+    static constexpr int count() { int n = 0; for (int ls = 0; ls < SB; ++ls) n += groups_of(ls); return n; }
+    static constexpr int kGroups = count();
+    static constexpr int stage(int gi) { int ls = 0; while (gi >= groups_of(ls)) gi -= groups_of(ls++); return ls; }
+    static constexpr int first(int gi) { int ls = 0; while (gi >= groups_of(ls)) gi -= groups_of(ls++); return gi * kPairs; }
+};
+
 // The two passes of the 16-per-lane forward transform on a lane's registers: in, a[k] = element r + L*k of the lane's polynomial
 // (|a| <= 2^31); out, a[k] = element 16 * lane' + k of the transform in the order algebra/ntt.py:271-291 leaves it (lane' = the
 // lane's index inside its polynomial), NOT reduced (|a| < 2^(34+SB)).  `row` is the polynomial's transpose buffer in LDS; the
 // caller has finished reading whatever the buffer held before (a wave_sync) and may write it again after the return.
-template <int LOGD, bool FAST, class TA>
+// `transposed` is called once the transpose buffer has been read back: from there on the wave's region is the caller's again.
+struct NoHook { __device__ __forceinline__ void operator()() const {} };
+
+template <int LOGD, bool FAST, bool STAGED = false, class TA, class HOOK = NoHook>
 __device__ __forceinline__ void fwd16_passes(double (&a)[16], double *row, const int r, const double2 *s_tw, const TA &twA,
-                                             const FzMod &m) {
+                                             const FzMod &m, const HOOK &transposed = HOOK()) {
     using G = Geom<LOGD>;
     constexpr int L = G::L, SB = G::SB;
     // strided pass: a 16-point LN transform over k with table entries 1..15 (|a| < 2^34 throughout)
@@ -180,46 +260,108 @@ __device__ __forceinline__ void fwd16_passes(double (&a)[16], double *row, const
         }
     }
     wave_sync();
+    transposed();
 
     // contiguous pass: stages with distance 2^(SB-1) .. 1, per-lane twiddles
+    if constexpr (!STAGED) {
 #pragma unroll
-    for (int ls = 0; ls < SB; ++ls) {
-        const int t = 1 << (SB - 1 - ls);
-        const int ebase = (16 >> SB) * ((1 << ls) - 1);
+        for (int ls = 0; ls < SB; ++ls) {
+            const int t = 1 << (SB - 1 - ls);
+            const int ebase = (16 >> SB) * ((1 << ls) - 1);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (k & t) continue;
-            const int g = k >> (SB - ls);
-            const double2 w = s_tw[(ebase + g) * L + r];
-            const double v = tw_mul<FAST>(a[k + t], w.x, w.y, m);
-            const double u = a[k];
-            a[k] = u + v;
-            a[k + t] = u - v;
+            for (int k = 0; k < 16; ++k) {
+                if (k & t) continue;
+                const int g = k >> (SB - ls);
+                const double2 w = s_tw[(ebase + g) * L + r];
+                const double v = tw_mul<FAST>(a[k + t], w.x, w.y, m);
+                const double u = a[k];
+                a[k] = u + v;
+                a[k + t] = u - v;
+            }
         }
+    } else {
+        // the same butterflies, their (w, w2) pairs read a GROUP ahead (TwGroups): the next group's reads are issued before
+        // this group's first multiply and nothing crosses the group's end, so a group's LDS round trip hides behind the
+        // one before and at most two groups of pairs (32 registers) are live
+        using TG = TwGroups<SB, true>;
+        double2 w[2][TwGroups<SB, true>::kPairs];
+        auto read = [&](auto gi_tag) __attribute__((always_inline)) {
+            constexpr int gi = decltype(gi_tag)::value, ls = TG::stage(gi), g0 = TG::first(gi);
+            constexpr int ebase = (16 >> SB) * ((1 << ls) - 1);
+#pragma unroll
+            for (int i = 0; i < TG::kPairs; ++i)
+                if (g0 + i < TG::pairs(ls)) w[gi & 1][i] = s_tw[(ebase + g0 + i) * L + r];
+        };
+        read(std::integral_constant<int, 0>());
+        static_for<TG::kGroups>([&](auto gi_tag) __attribute__((always_inline)) {
+            constexpr int gi = decltype(gi_tag)::value, ls = TG::stage(gi), g0 = TG::first(gi);
+            if constexpr (gi + 1 < TG::kGroups) read(std::integral_constant<int, gi + 1>());
+            constexpr int t = 1 << (SB - 1 - ls);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int g = k >> (SB - ls);
+                if ((k & t) || g < g0 || g >= g0 + TG::kPairs) continue;
+                const double2 ww = w[gi & 1][g - g0];
+                const double v = tw_mul<FAST>(a[k + t], ww.x, ww.y, m);
+                const double u = a[k];
+                a[k] = u + v;
+                a[k + t] = u - v;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
     }
 }
 
 // ... and of the inverse: in, a[k] = element 16 * lane' + k (|a| <= 2^31); out, a[k] = element r + L*k, scaled by n^-1, NOT
 // centred (|a| <= q/2 + q * 2^-13: every output has passed the last stage's multiply).
-template <int LOGD, bool FAST, class TA>
+template <int LOGD, bool FAST, bool STAGED = false, class TA, class HOOK = NoHook>
 __device__ __forceinline__ void inv16_passes(double (&a)[16], double *row, const int r, const double2 *s_tw, const TA &twA,
-                                             const FzMod &m) {
+                                             const FzMod &m, const HOOK &transposed = HOOK()) {
     using G = Geom<LOGD>;
     constexpr int L = G::L, SB = G::SB;
     // contiguous pass: GS stages with distance 1, 2, .. 2^(SB-1); operands |u - v| <= 2^(32+ls)
+    if constexpr (!STAGED) {
 #pragma unroll
-    for (int ls = 0; ls < SB; ++ls) {
-        const int t = 1 << ls;
-        const int ebase = 16 - (16 >> ls);
+        for (int ls = 0; ls < SB; ++ls) {
+            const int t = 1 << ls;
+            const int ebase = 16 - (16 >> ls);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (k & t) continue;
-            const int g = k >> (ls + 1);
-            const double2 w = s_tw[(ebase + g) * L + r];
-            const double u = a[k], v = a[k + t];
-            a[k] = u + v;
-            a[k + t] = tw_mul<FAST>(u - v, w.x, w.y, m);
+            for (int k = 0; k < 16; ++k) {
+                if (k & t) continue;
+                const int g = k >> (ls + 1);
+                const double2 w = s_tw[(ebase + g) * L + r];
+                const double u = a[k], v = a[k + t];
+                a[k] = u + v;
+                a[k + t] = tw_mul<FAST>(u - v, w.x, w.y, m);
+            }
         }
+    } else {
+        // pairs read a group ahead: see fwd16_passes
+        using TG = TwGroups<SB, false>;
+        double2 w[2][TwGroups<SB, false>::kPairs];
+        auto read = [&](auto gi_tag) __attribute__((always_inline)) {
+            constexpr int gi = decltype(gi_tag)::value, ls = TG::stage(gi), g0 = TG::first(gi);
+            constexpr int ebase = 16 - (16 >> ls);
+#pragma unroll
+            for (int i = 0; i < TG::kPairs; ++i)
+                if (g0 + i < TG::pairs(ls)) w[gi & 1][i] = s_tw[(ebase + g0 + i) * L + r];
+        };
+        read(std::integral_constant<int, 0>());
+        static_for<TG::kGroups>([&](auto gi_tag) __attribute__((always_inline)) {
+            constexpr int gi = decltype(gi_tag)::value, ls = TG::stage(gi), g0 = TG::first(gi);
+            if constexpr (gi + 1 < TG::kGroups) read(std::integral_constant<int, gi + 1>());
+            constexpr int t = 1 << ls;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int g = k >> (ls + 1);
+                if ((k & t) || g < g0 || g >= g0 + TG::kPairs) continue;
+                const double2 ww = w[gi & 1][g - g0];
+                const double u = a[k], v = a[k + t];
+                a[k] = u + v;
+                a[k + t] = tw_mul<FAST>(u - v, ww.x, ww.y, m);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
     }
 
     // After the contiguous pass a[0] (the sum of the lane's 16 inputs, up to 2^(31+SB)) is the one value no multiply
@@ -236,6 +378,7 @@ __device__ __forceinline__ void inv16_passes(double (&a)[16], double *row, const
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = (row + r)[pad16(L * k)];       // = row[pad16(r + L * k)] (see fwd16_passes)
     wave_sync();
+    transposed();
 
     // strided pass: GS stages with distance L, 2L, 4L, 8L; uniform twiddles; n^-1 folded into the last stage.
     // Operands stay below 2^38 (see the fold above), so every stage uses the 4-op multiply when the modulus admits it.
@@ -256,7 +399,29 @@ __device__ __forceinline__ void inv16_passes(double (&a)[16], double *row, const
                 a[k + tk] = tw_mul<FAST>(u - v, twA.w[e], twA.w2[e], m);
             }
         }
+        if constexpr (STAGED) __builtin_amdgcn_sched_barrier(0);      // a stage's eight butterflies interleave, stages do not: the 6-op multiply's temporaries of two stages at once cost 8-14 registers
     }
+}
+
+// does an unpadded chunk fit a wave's region behind the staging image (the landing area of chunk_load_lds)?
+template <int LOGD> constexpr bool landing_fits() {
+    using G = Geom<LOGD>;
+    return G::PPW * G::PS * 8 - kLandOff * 4 >= kChunk * 4 && (kLandOff * 4) % 16 == 0;
+}
+
+// the order of a wave's iterations: `whole` chunks lie inside the batch, a ragged last one (tasks == whole + 1) does not.
+// iteration(task, NEXT, LANDED): NEXT, the wave's next chunk is whole and is requested during this iteration; LANDED, this
+// one is whole and was.  The ragged chunk is a batch's last task and one wave's: it loads its own chunk (see fwd16_run).
+template <class IT>
+__device__ __forceinline__ void run16_chunks(const size_t first, const size_t stride, const size_t tasks, const size_t whole,
+                                             const IT &iteration) {
+    size_t task = first;
+    if (task < whole) {
+        for (; task + stride < whole; task += stride) iteration(task, std::true_type(), std::true_type());
+        iteration(task, std::false_type(), std::true_type());
+        task += stride;
+    }
+    if (task < tasks) iteration(task, std::false_type(), std::false_type());
 }
 
 // the whole forward kernel as a function of (block index, blocks that share the batch): ntt_fwd16 runs it over the grid,
@@ -268,6 +433,8 @@ __device__ __forceinline__ void fwd16_run(const int32_t *in, int32_t *out, size_
     constexpr int D = G::D, L = G::L, PPW = G::PPW, SB = G::SB, NE = G::NE, PS = G::PS;
     constexpr int REGION = PPW * PS;                      // doubles per wave
     static_assert(REGION * 2 >= kStageWords, "staging image must fit in the transpose buffer");
+    static_assert(landing_fits<LOGD>() && landing_fits<5>() && landing_fits<6>() && landing_fits<7>() && landing_fits<8>(),
+                  "a 4 KiB chunk must fit the wave's region behind the staging image, at every degree the bodies serve");
     double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);      // (w, w2) pairs, [NE][L]
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;      // the wave index is uniform: say so (scalar address arithmetic)
@@ -278,44 +445,50 @@ __device__ __forceinline__ void fwd16_run(const int32_t *in, int32_t *out, size_
     const size_t stride = (size_t)nblocks * kWavesPerBlock;
     // the wave's first chunk is requested BEFORE the twiddle table is staged: two memory latencies overlapped instead of added (a
     // launch of 2^16 rows is four iterations per wave: a microsecond of start-up is 4 % of it)
-    Chunk raw0 = {};
-    if (first < tasks) raw0 = chunk_load(in, first, total, lane);
-    for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
-    __syncthreads();                                      // the only workgroup-wide barrier
+    const size_t whole = total / kChunk;                  // chunks that lie inside the batch: all but a ragged last one
     double *region = lds + wave * REGION;
     int32_t *stage = reinterpret_cast<int32_t *>(region);
+    int32_t *land = stage + kLandOff;
+    if (first < whole) chunk_load_lds(in, first, lane, land);          // nothing else is in the region yet
+    for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
+    chunk_landed<0>();
+    __syncthreads();                                      // the only workgroup-wide barrier
     double *row = region + p * PS;
     if (first >= tasks) return;
     // Software pipeline.  gfx9 has ONE in-order counter (vmcnt) for loads and stores, so a wait for a
     // prefetched load also waits for every store issued before... and, at a loop header, the compiler must
-    // assume the worst over all entry paths.  Each iteration therefore (1) issues the NEXT chunk's loads
-    // first, (2) computes, (3) moves the finished outputs LDS -> registers, (4) waits for the prefetched
-    // chunk and stages it into LDS, and only then (5) issues the global stores: the stores are always the
-    // youngest outstanding operations and nothing waits for their completion until a whole iteration later.
-    chunk_to_lds(stage, lane, raw0);
+    // assume the worst over all entry paths.  A whole chunk comes by chunk_load_lds into the LANDING AREA, the 4 KiB of the
+    // wave's region behind the staging image: the transposed doubles cover it only between the transpose's write and read, so
+    // an iteration (1) reads its inputs from the landing area, (2) computes up to the transpose, (3) requests the NEXT chunk
+    // into the landing area, (4) computes the rest and moves the outputs through the staging image, (5) issues the global
+    // stores and (6) waits until all but those four stores have retired (chunk_landed<4>): the chunk has had the second
+    // half of the iteration to arrive, the stores have a whole iteration, and the chunk holds no register meanwhile.
 
-    // One iteration; MORE = another chunk of this wave follows (its loads are issued first).  The loop runs the MORE form and
-    // the wave's last chunk is peeled off as the other: rounds 1-4 issued the loads unconditionally and re-loaded the CURRENT
-    // chunk on a wave's last iteration (a quarter more read requests at the four iterations of a multi-job launch: the PMC pass
-    // over round 5's headline read 78.2 MB per launch where 64 MiB are due), and a run-time `if (more)` around loads and staging
-    // made the compiler wait for ALL memory operations -- the previous iteration's stores -- at the loop header (two
-    // branches on one condition are two paths to its wait-count pass): 3-8 % on the stand-alone kernels.
-    auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {
-        constexpr bool more = decltype(more_tag)::value;
-        Chunk raw = {};
-        if (more) raw = chunk_load(in, task + stride, total, lane);
+    // One iteration.  NEXT: another WHOLE chunk of this wave follows and is requested here.  LANDED: this chunk is whole and its
+    // inputs are in the landing area; else it is the ragged last chunk of the batch -- one wave's last task -- and takes the
+    // register path every chunk took through round 11 (chunk_load clamps, chunk_to_lds stages the padded image, chunk_store
+    // predicates), loaded at the top of its own iteration: prefetched, its sixteen registers would set the peak of every kernel
+    // for the sake of one wave per batch.  The forms are peeled (run16_chunks), not branched: a run-time condition around
+    // loads made the compiler wait for ALL memory operations -- the previous iteration's stores -- at the loop header (rounds
+    // 1-5: 3-8 % on the stand-alone kernels), and chunk_landed<4> counts on exactly four stores behind the request.
+    auto iteration = [&](const size_t task, auto next_tag, auto landed_tag) __attribute__((always_inline)) {
+        constexpr bool next = decltype(next_tag)::value;
+        constexpr bool landed = decltype(landed_tag)::value;
+        if constexpr (!landed) chunk_to_lds(stage, lane, chunk_load(in, task, total, lane));
         wave_sync();
         double a[16];
         {
             int x[16];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) x[k] = stage[pad4(p * D + r + L * k)];
+            for (int k = 0; k < 16; ++k) x[k] = landed ? land[p * D + r + L * k] : (stage + pad4(p * D) + r)[pad4(L * k)];      // = stage[pad4(p * D + r + L * k)]: r < L and L divides 16
 #pragma unroll
             for (int k = 0; k < 16; ++k) a[k] = (double)x[k];
         }
         wave_sync();
 
-        fwd16_passes<LOGD, FAST>(a, row, r, s_tw, twA, m);
+        fwd16_passes<LOGD, FAST, true>(a, row, r, s_tw, twA, m, [&]() __attribute__((always_inline)) {
+            if constexpr (next) chunk_load_lds(in, task + stride, lane, land);
+        });
 
         // lane holds chunk elements [16*lane, 16*lane + 16): centre, stage, store coalesced
 #pragma unroll
@@ -327,18 +500,17 @@ __device__ __forceinline__ void fwd16_run(const int32_t *in, int32_t *out, size_
             o.w = (int)fz_cent(a[4 * k + 3], m);
             *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = o;
         }
-        wave_sync();
+        wave_sync_inflight();
         const int4 o0 = *reinterpret_cast<const int4 *>(stage + pad4(4 * lane));
         const int4 o1 = *reinterpret_cast<const int4 *>(stage + pad4(256 + 4 * lane));
         const int4 o2 = *reinterpret_cast<const int4 *>(stage + pad4(512 + 4 * lane));
         const int4 o3 = *reinterpret_cast<const int4 *>(stage + pad4(768 + 4 * lane));
-        wave_sync();
-        if (more) chunk_to_lds(stage, lane, raw);   // waits for the prefetched loads (no store is younger)
-        chunk_store<PLAIN>(out, task, total, lane, o0, o1, o2, o3);
+        wave_sync_inflight();
+        if constexpr (landed) chunk_store_whole<PLAIN>(out, task, lane, o0, o1, o2, o3);
+        else chunk_store<PLAIN>(out, task, total, lane, o0, o1, o2, o3);
+        if constexpr (next) chunk_landed<4>();
     };
-    size_t task = first;
-    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
-    iteration(task, std::false_type());
+    run16_chunks(first, stride, tasks, whole, iteration);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -358,25 +530,26 @@ __device__ __forceinline__ void inv16_run(const int32_t *in, int32_t *out, size_
     const size_t tasks = (total + kChunk - 1) / kChunk;
     const size_t first = (size_t)block * kWavesPerBlock + wave;
     const size_t stride = (size_t)nblocks * kWavesPerBlock;
-    Chunk raw0 = {};
-    if (first < tasks) raw0 = chunk_load(in, first, total, lane);      // before the table: see fwd16_run
-    for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = itwB[i];
-    __syncthreads();
+    const size_t whole = total / kChunk;
     double *region = lds + wave * REGION;
     int32_t *stage = reinterpret_cast<int32_t *>(region);
+    int32_t *land = stage + kLandOff;
+    if (first < whole) chunk_load_lds(in, first, lane, land);          // before the table, landing area, waits: see fwd16_run
+    for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = itwB[i];
+    chunk_landed<0>();
+    __syncthreads();
     double *row = region + p * PS;
     if (first >= tasks) return;
-    chunk_to_lds(stage, lane, raw0);
 
-    auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {       // pipeline and peeling: see fwd16_run
-        constexpr bool more = decltype(more_tag)::value;
-        Chunk raw = {};
-        if (more) raw = chunk_load(in, task + stride, total, lane);
+    auto iteration = [&](const size_t task, auto next_tag, auto landed_tag) __attribute__((always_inline)) {       // pipeline and peeling: see fwd16_run
+        constexpr bool next = decltype(next_tag)::value;
+        constexpr bool landed = decltype(landed_tag)::value;
+        if constexpr (!landed) chunk_to_lds(stage, lane, chunk_load(in, task, total, lane));
         wave_sync();
         double a[16];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int4 t = *reinterpret_cast<const int4 *>(stage + pad4(16 * lane + 4 * k));
+            const int4 t = *reinterpret_cast<const int4 *>(landed ? land + 16 * lane + 4 * k : stage + pad4(16 * lane + 4 * k));
             a[4 * k + 0] = (double)t.x;
             a[4 * k + 1] = (double)t.y;
             a[4 * k + 2] = (double)t.z;
@@ -384,22 +557,23 @@ __device__ __forceinline__ void inv16_run(const int32_t *in, int32_t *out, size_
         }
         wave_sync();
 
-        inv16_passes<LOGD, FAST>(a, row, r, s_tw, twA, m);
+        inv16_passes<LOGD, FAST, true>(a, row, r, s_tw, twA, m, [&]() __attribute__((always_inline)) {
+            if constexpr (next) chunk_load_lds(in, task + stride, lane, land);
+        });
 
 #pragma unroll
-        for (int k = 0; k < 16; ++k) stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
-        wave_sync();
+        for (int k = 0; k < 16; ++k) (stage + pad4(p * D) + r)[pad4(L * k)] = (int)fz_cent(a[k], m);      // = stage[pad4(p * D + r + L * k)]: r < L and L divides 16 (constant offsets)
+        wave_sync_inflight();
         const int4 o0 = *reinterpret_cast<const int4 *>(stage + pad4(4 * lane));
         const int4 o1 = *reinterpret_cast<const int4 *>(stage + pad4(256 + 4 * lane));
         const int4 o2 = *reinterpret_cast<const int4 *>(stage + pad4(512 + 4 * lane));
         const int4 o3 = *reinterpret_cast<const int4 *>(stage + pad4(768 + 4 * lane));
-        wave_sync();
-        if (more) chunk_to_lds(stage, lane, raw);
-        chunk_store<PLAIN>(out, task, total, lane, o0, o1, o2, o3);
+        wave_sync_inflight();
+        if constexpr (landed) chunk_store_whole<PLAIN>(out, task, lane, o0, o1, o2, o3);
+        else chunk_store<PLAIN>(out, task, total, lane, o0, o1, o2, o3);
+        if constexpr (next) chunk_landed<4>();
     };
-    size_t task = first;
-    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
-    iteration(task, std::false_type());
+    run16_chunks(first, stride, tasks, whole, iteration);
 }
 
 // ------------------------------------------------------------------------------------------
