@@ -445,6 +445,29 @@ int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_
     return fz_launch_aggregate_encoded(ctx, d_bytes, d_alpha_hat, d_skip, N, l, w, bound, d_partial, d_out);
 }
 
+int fz_verify_encoded_async(fz_ctx *ctx, const int32_t *d_A, const uint8_t *d_bytes, size_t N, int l, int64_t bound,
+                            const int32_t *d_target, const int32_t *d_vk, const int32_t *d_c_hat, int *d_verdicts) {
+    FZ_REQUIRE(ctx && l >= 1, "bad argument");
+    FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "bound %lld outside [1, (q-1)/2]", (long long)bound);
+    FZ_REQUIRE((d_target != nullptr) != (d_vk != nullptr || d_c_hat != nullptr) && (d_vk != nullptr) == (d_c_hat != nullptr),
+               "exactly one of d_target, or the pair d_vk and d_c_hat, must be given");
+    if (N == 0) return FZ_OK;
+    FZ_REQUIRE(d_A && d_bytes && d_verdicts, "NULL argument");
+    FZ_REQUIRE((((uintptr_t)d_bytes | (uintptr_t)d_A) & 15) == 0, "the bytes and A must be 16-byte aligned");
+    FZ_REQUIRE((((uintptr_t)d_target | (uintptr_t)d_vk | (uintptr_t)d_c_hat | (uintptr_t)d_verdicts) & 3) == 0,
+               "target, keys, challenges and verdicts must be 4-byte aligned");
+    if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
+    FZ_REQUIRE((uint64_t)l * (uint64_t)ctx->degree <= 0x7fffffffull && N <= ((size_t)-1 >> 3) / ((size_t)l * ctx->degree),
+               "%zu records of %d rows are too many", N, l);
+    int w = 0;
+    while ((2 * bound) >> w) ++w;
+    const size_t rb = (size_t)l * ctx->degree / 8 * (size_t)w;
+    if (rb % 16 != 0) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: the verification from bytes needs a multiple of 16", rb);
+    if (rb > 0xffffffffull) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes are too long", rb);
+    FZ_DEV(ctx);
+    return fz_launch_verify_encoded(ctx, d_A, d_bytes, N, l, w, bound, d_target, d_vk, d_c_hat, d_verdicts);
+}
+
 int fz_verify_partials_batch_async(fz_ctx *ctx, const int32_t *d_A, const int64_t *d_partial, size_t partial_stride,
                                    const int64_t *d_target_partial, size_t target_stride, size_t groups, int l,
                                    int64_t beta_vf, int64_t omega_vf, int *d_verdicts) {

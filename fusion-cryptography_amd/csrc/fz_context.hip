@@ -348,7 +348,7 @@ int fz_ctx_destroy(fz_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     // the fixed tables and the lazily built ones
-    void *const fixed[] = {ctx->d_tw, ctx->d_itw, ctx->d_tw2, ctx->d_itw2, ctx->d_twB, ctx->d_itwB, ctx->d_twAB, ctx->d_mt_init, ctx->d_diag};
+    void *const fixed[] = {ctx->d_tw, ctx->d_itw, ctx->d_tw2, ctx->d_itw2, ctx->d_twB, ctx->d_itwB, ctx->d_twAB, ctx->d_mt_init, ctx->d_diag, ctx->d_venc};
     for (void *p : fixed)
         if (p) (void)hipFree(p);
     for (FzArea &a : ctx->area)

@@ -82,6 +82,11 @@ struct fz_ctx {
     int grid_pm16;               // ... of its 16-per-lane form
     int grid_rec[4];             // ... of the byte-encoding kernels: [encode, decode] x [coefficient kinds, keys] (degree 64 / 256)
     int grid_aggenc, grid_check; // ... of aggregate_encoded and encoded_check (fz_aggregate_encoded.hip; degree 64 / 256)
+    // verification from the bytes with several workgroups per record (fz_verify_encoded.hip; degree 64 / 256): a slot of int64 sums
+    // and a status word per record, venc_bytes in all; allocated once at context creation (fz_verify_encoded_setup), never grown --
+    // the entry is allocation-free and capturable from its first call -- and released by fz_ctx_destroy
+    unsigned long long *d_venc;
+    size_t venc_bytes;
     int knob_ntt_rows;           // FZ_NTT_ROWS = 1 | 2 | 4: row groups per wave of the radix-4 kernels (0 = by batch size)
     // per-dispatch timing of the NTT kernels (fz_profile_begin/end): event pairs bound to the
     // dispatch itself via hipExtLaunchKernelGGL, i.e. kernel begin -> kernel end on its own stream
@@ -272,10 +277,17 @@ int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_
 // (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from
 // their bytes: d_partial [l][degree] int64 zeroed, then sum_i cent(NTT(z_i) (.) alpha_hat_i) over the signers with skip[i] == 0
 // (skip NULL: all), d_out = cent(d_partial) when not NULL.  Records of the aggregation are multiples of 16 bytes.
-int fz_aggregate_encoded_query_grid(fz_ctx *ctx);                  // ctx->grid_aggenc, ctx->grid_check (context creation)
+int fz_aggregate_encoded_query_grid(fz_ctx *ctx);                  // ctx->grid_aggenc, ctx->grid_check, then fz_verify_encoded_setup (context creation)
 int fz_launch_check_records(fz_ctx *ctx, const uint8_t *bytes, size_t n, int rows, int w, int64_t bound, int *d_status);
 int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, int l, int w,
                                 int64_t bound, int64_t *d_partial, int32_t *d_out);
+
+// verification straight from the bytes (fz_verify_encoded.hip; degree 64 / 256): d_verdict [N] = 0, FZ_VERDICT_TARGET_MISMATCH or
+// FZ_VERDICT_ENCODING of N records of l rows against `target` [N][degree] (any residues) or, when vk != NULL, against
+// cent(vkL (.) c + vkR) from vk [N][2][degree] and chal [N][degree].  Records are multiples of 16 bytes.
+int fz_verify_encoded_setup(fz_ctx *ctx);                          // ctx->d_venc (context creation: fz_aggregate_encoded_query_grid calls it)
+int fz_launch_verify_encoded(fz_ctx *ctx, const int32_t *A, const uint8_t *bytes, size_t N, int l, int w, int64_t bound,
+                             const int32_t *target, const int32_t *vk, const int32_t *chal, int *d_verdict);
 
 // fused keygen and verification (fz_scheme_fused.hip)
 int fz_launch_keygen_fused(fz_ctx *ctx, const int32_t *A, const int32_t *coef, int32_t *sk_hat, int32_t *vk, size_t segments,

@@ -620,6 +620,50 @@ def aggregate_from_bytes(params: Params, keys: List[OneTimeVerificationKey], mes
     return Signature(signature_hat=_column(params, out))
 
 
+def verify_signatures_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
+                                 blobs: List[bytes]) -> List[Tuple[bool, str]]:
+    """NOT in the reference: verify_signatures() of signatures given as their compact bytes (one "signature" record of
+    to_bytes each), without ever expanding them -> [(ok, reason)] per signer (BatchScheme.verify_signatures_encoded).  A record
+    that is not canonical reports (False, "Encoding is not canonical."), a signature that misses its key's target (False,
+    "Target doesn't match image of signature.").  Raises ValueError for unequal numbers of keys, messages and blobs and for a
+    blob of the wrong length (with its index)."""
+    from fusion_hip import ENCODING_REASONS, SIGNATURE_REASONS
+    from fusion_hip.scheme import BatchScheme, encoded_size, vk_from_object
+    if not (len(keys) == len(messages) == len(blobs)):
+        raise ValueError(f"{len(keys)} keys, {len(messages)} messages, {len(blobs)} records")
+    size = encoded_size(params, "signature")
+    for i, b in enumerate(blobs):
+        if len(b) != size:
+            raise ValueError(f"record {i}: a 'signature' record is {size} bytes, not {len(b)}")
+    if not blobs:
+        return []
+    vk = np.stack([vk_from_object(params, k) for k in keys])
+    bs = BatchScheme(params)
+    try:
+        codes = bs.verify_signatures_encoded(vk, list(messages), b"".join(bytes(b) for b in blobs))
+    finally:
+        bs.close()
+    return [(int(c) == 0, ENCODING_REASONS[6] if int(c) == 6 else SIGNATURE_REASONS[int(c)]) for c in codes]
+
+
+def verify_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str], blob: bytes) -> Tuple[bool, str]:
+    """NOT in the reference: verify() of an aggregate given as its compact bytes (the "aggregate" record of to_bytes(...,
+    aggregate=True)), without expanding it -> (ok, reason) as verify(params, keys, messages, from_bytes(params, "aggregate",
+    blob)) gives it (BatchScheme.verify_encoded); a record that is not canonical reports (False, "Encoding is not
+    canonical.").  Raises ValueError for a blob of the wrong length."""
+    from fusion_hip.scheme import BatchScheme, encoded_size, vk_from_object
+    size = encoded_size(params, "aggregate")
+    if len(blob) != size:
+        raise ValueError(f"an 'aggregate' record is {size} bytes, not {len(blob)}")
+    d = params.degree
+    vk = np.stack([vk_from_object(params, k) for k in keys]) if len(keys) else np.zeros((0, 2, d), dtype=np.int32)
+    bs = BatchScheme(params)
+    try:
+        return bs.verify_encoded(vk, list(messages), bytes(blob))
+    finally:
+        bs.close()
+
+
 _ORIGINALS.update({name: globals()[name] for name in (
     "decode_bytes_to_polynomial_coefficients", "hash_ch", "parse_challenge", "transform", "sample_coefficient_matrix", "hash_ag",
     "sample_polynomial_coefficient_representation")})

@@ -421,6 +421,13 @@ class Context:
         check(self._lib, self._lib.fz_aggregate_encoded_async(self._h, c_void_p(d_bytes), c_void_p(d_alpha), c_void_p(d_skip or None),
                                                               N, l, bound, c_void_p(d_partial), c_void_p(d_out or None)))
 
+    def verify_encoded_async_dev(self, d_A, d_bytes, N, l, bound, d_target, d_vk, d_c_hat, d_verdicts):
+        """the verdicts (0, 3, 6) of N encoded records of l rows straight from their bytes, against d_target [N][d] or, with
+        d_target 0 / None, against the targets formed from d_vk [N][2][d] and d_c_hat [N][d] (asynchronous)"""
+        check(self._lib, self._lib.fz_verify_encoded_async(self._h, c_void_p(d_A), c_void_p(d_bytes), N, l, bound,
+                                                           c_void_p(d_target or None), c_void_p(d_vk or None),
+                                                           c_void_p(d_c_hat or None), c_void_p(d_verdicts)))
+
     def reduce_i64_dev(self, d_in, d_out, count):
         check(self._lib, self._lib.fz_reduce_i64(self._h, c_void_p(d_in), c_void_p(d_out), count))
 

@@ -559,8 +559,8 @@ class BatchScheme:
         and the key sort), and one fused pass unpacks, transforms, multiplies and accumulates them: the int32 rows of the
         signatures (2.46 times the bytes at secpar 256) never exist on the device.
         What this call does NOT do: a canonical record is within the norm bound of ONE signature, but its target equation
-        A (.) sig_i == vkL_i (.) c_i + vkR_i is not checked.  An aggregator of untrusted input verifies its own aggregate
-        (verify); when that fails it falls back to decode + aggregate_screened, which names the signer.
+        A (.) sig_i == vkL_i (.) c_i + vkR_i is not checked.  An aggregator of mostly honest input verifies its own aggregate
+        (verify); when that fails, aggregate_encoded_screened on the same bytes names the signer.
         A length that is not N whole records, or numbers of keys / messages other than N, raise FusionHipError(FZ_E_BADARG)
         before the device is touched."""
         nrows, _, bound, _, rb = _encoding(self.params, "signature")
@@ -597,6 +597,109 @@ class BatchScheme:
             for b, o in ((dB, own), (dV, True), (dAl, True), (dP, True), (dO, True)):
                 if o and b is not None:
                     b.free()
+
+    # ---- verification straight from the bytes (not in the reference) ---------------------
+    def _screen_encoded(self, vk, messages, data, aggregate):
+        """verify_signatures_encoded, and with aggregate=True the screened aggregation behind it: -> (aggregate or None,
+        codes).  The argument checks come before anything touches the device."""
+        nrows, _, bound, _, rb = _encoding(self.params, "signature")
+        data, n = _records_input("signature", data, rb)
+        nk = vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+        if not (nk == len(messages) == n):
+            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
+        if isinstance(vk, DeviceArray) and (vk.shape != (n, 2, self.d) or vk.dtype != np.int32):
+            raise FusionHipError(FZ_E_BADARG, f"device array {vk.shape} {vk.dtype}: {(n, 2, self.d)} int32 expected")
+        if n == 0:
+            return None, np.zeros(0, dtype=np.int32)
+        own_b = not isinstance(data, DeviceArray)
+        dB = dK = dC = dV = dAl = dP = dO = None
+        own_k = False
+        try:
+            dB = DeviceArray.from_numpy(self.ctx, data.reshape(n, rb)) if own_b else data
+            dK, own_k = self._dev(vk, (n, 2, self.d))
+            c_hat = pre = None
+            if self.device_hash:
+                try:
+                    dC, pre = self.challenges_dev(dK, messages, want_prehash=aggregate)
+                    c_hat = dC.numpy() if aggregate else None
+                except FusionHipError as e:
+                    if e.code != FZ_E_UNSUPPORTED:
+                        raise
+                    self.device_hash = False
+            if dC is None:                                   # the host pipeline: parameter sets the device one does not cover
+                c_hat, pre = self.challenges(dK, messages)
+                dC = DeviceArray.from_numpy(self.ctx, c_hat)
+            dV = DeviceArray(self.ctx, (n,))
+            self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
+            codes = dV.numpy()
+            valid = codes == 0
+            if not aggregate or not valid.any():
+                return None, codes
+            _, L, R = self._split_vk(vk)
+            _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads)
+            dAl = DeviceArray.from_numpy(self.ctx, alpha)
+            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
+            dP, dO = DeviceArray(self.ctx, (self.l, self.d), np.int64), DeviceArray(self.ctx, (self.l, self.d))
+            # the verdict words as they are: a record with any code but 0 is skipped, its bytes not read again
+            self.ctx.aggregate_encoded_async_dev(dB.ptr, dAl.ptr, dV.ptr, n, self.l, bound, dP.ptr, dO.ptr)
+            return dO.numpy(), codes
+        finally:
+            for b, o in ((dB, own_b), (dK, own_k), (dC, True), (dV, True), (dAl, True), (dP, True), (dO, True)):
+                if o and b is not None:
+                    b.free()
+
+    def verify_signatures_encoded(self, vk, messages, data):
+        """verify_signatures straight from the signatures' compact bytes (`data`: N "signature" records in every form decode
+        takes; vk [N][2][d] numpy or DeviceArray): -> int32 codes [N].  codes[i] is 6 (ENCODING_REASONS) when record i is not
+        canonical (a field above 2B) -- it then has no value to test, so this comes first --, else 3 (SIGNATURE_REASONS) when
+        A (.) sig_i != vkL_i (.) c_i + vkR_i, else 0.  Codes 4 and 5 cannot occur: a canonical record is within the bound of
+        one signature by construction, and the weight bound omega_vf = d cannot fail.  For canonical records the codes equal
+        verify_signatures(vk, messages, decode("signature", data)[0]).  One upload of the bytes, one challenge pass, one launch,
+        one verdict download; the int32 rows of the signatures never exist on the device.  A length that is not N whole records,
+        or numbers of keys / messages other than N, raise FusionHipError(FZ_E_BADARG) before the device is touched."""
+        return self._screen_encoded(vk, messages, data, False)[1]
+
+    def aggregate_encoded_screened(self, vk, messages, data):
+        """aggregate_screened straight from the bytes: -> (aggregate [l][d] or None when no signer passes, codes [N] of
+        verify_signatures_encoded).  The verdict words stay on the device and are the skip words of the fused aggregation, so
+        a rejected record is not read a second time; hash_ag runs over the signers with code 0 only.  The aggregate is bit
+        for bit aggregate_screened(vk, messages, decode("signature", data)[0])[0]: a record that is not canonical (code 6
+        here) decodes to zero rows, which that call rejects as well."""
+        return self._screen_encoded(vk, messages, data, True)
+
+    def verify_encoded(self, vk, messages, data):
+        """verify() of an aggregate given as ONE "aggregate" record (every form decode takes): -> (bool, reason), equal to
+        verify(vk, messages, decode("aggregate", data)[0][0]) for a canonical record; a record that is not canonical gives
+        (False, ENCODING_REASONS[6]).  The aggregate's int32 rows never exist on the device.  Anything but exactly one whole
+        record raises FusionHipError(FZ_E_BADARG) before the device is touched."""
+        _, _, bound, _, rb = _encoding(self.params, "aggregate")
+        data, nrec = _records_input("aggregate", data, rb)
+        if nrec != 1:
+            raise FusionHipError(FZ_E_BADARG, f"{nrec} 'aggregate' records: exactly one expected")
+        n = (vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0])
+        if n > self.params.capacity:
+            return False, VERDICT_REASONS[1]
+        if n != len(messages):
+            return False, VERDICT_REASONS[2]
+        own = not isinstance(data, DeviceArray)
+        dC, dAl, _, L, R = self.hash_ag_dev(vk, messages)
+        bufs = [dC, dAl]
+        try:
+            dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
+            bufs += [dL, dR]
+            dB = DeviceArray.from_numpy(self.ctx, data.reshape(1, rb)) if own else data
+            if own:
+                bufs.append(dB)
+            dT64, dT, dV = DeviceArray(self.ctx, (self.d,), np.int64), DeviceArray(self.ctx, (self.d,)), DeviceArray(self.ctx, (1,))
+            bufs += [dT64, dT, dV]
+            self.ctx.target_partial_dev(dL.ptr, dR.ptr, dC.ptr, dAl.ptr, dT64.ptr, n)
+            self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, self.d)
+            self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, 1, self.l, bound, dT.ptr, 0, 0, dV.ptr)
+            code = int(dV.numpy()[0])
+            return code == 0, (ENCODING_REASONS[6] if code == 6 else VERDICT_REASONS[code])
+        finally:
+            for b in bufs:
+                b.free()
 
     # ---- many aggregates at once ------------------------------------------------------------------------
     def _hash_ag_many(self, vk, messages, sizes):

@@ -351,6 +351,23 @@ FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n,
 FZ_API int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
                                       size_t N, int l, int64_t bound, int64_t *d_partial, int32_t *d_out);
 
+/* verdicts of N encoded records against their targets, straight from the bytes */
+/* Record i is l rows of w-bit fields u = z + bound, z = cent(INTT(row)), exactly what fz_encode_records_async writes for a
+ * signature or an aggregate.  d_verdicts[i] = FZ_VERDICT_ENCODING (6) when some field of record i is above 2 * bound (the
+ * record then has no defined value: this comes first), else FZ_VERDICT_TARGET_MISMATCH (3) when sum_k NTT(z_k) (.) A_k differs
+ * from the target mod q, else 0.  FZ_VERDICT_NORM (4) and FZ_VERDICT_WEIGHT (5) cannot occur: a canonical record is within
+ * `bound` by construction, and the encoding never carried a weight check.  Exactly one form of the target is given, the other
+ * pointer(s) NULL (else FZ_E_BADARG): d_target [N][degree], any int32 residues, or the pair d_vk [N][2][degree] +
+ * d_c_hat [N][degree], from which the target cent(vkL (.) c + vkR) of ONE signer is formed as fz_verify_signatures_async
+ * forms it.  d_A [l][degree] takes any int32 value.  Rules of fz_aggregate_encoded_async: degree 64 or 256 (else
+ * FZ_E_UNSUPPORTED), 1 <= bound <= (q-1)/2, l >= 1 (l >= 2^22: FZ_E_UNSUPPORTED, the sums would not be exact), d_bytes and d_A
+ * 16-byte aligned, the other pointers 4-byte aligned, records that are no multiple of 16 bytes FZ_E_UNSUPPORTED, N == 0 does
+ * nothing and writes nothing.  The bytes are never written; nothing behind d_verdicts[N - 1] is.  Asynchronous on the context's
+ * stream, allocation-free (the int64 area that several workgroups of one record share when N is small belongs to the context
+ * from its creation on and is cleared by the call itself, as part of the captured work), capturable by fz_graph_*. */
+FZ_API int fz_verify_encoded_async(fz_ctx *ctx, const int32_t *d_A, const uint8_t *d_bytes, size_t N, int l, int64_t bound,
+                                   const int32_t *d_target, const int32_t *d_vk, const int32_t *d_c_hat, int *d_verdicts);
+
 /* ---- the exchange step across GPUs: RCCL all-reduce of the int64 partial sums -------------------
  * aggregate() (fusion.py:670-676) and verify()'s target (:706-714) are sums over signers; with the signers sharded over
  * GPUs each rank holds exact int64 partials (fz_aggregate_partial*, fz_target_partial*, fz_aggregate_target_partial_batch)
