@@ -56,18 +56,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void encoded_check(const uint8
 // in-order memory counter and waiting for it does not wait for the prefetch.
 // The lanes of a tail chunk past the record's end read nothing (packed_load stops at the record's length); what they compute from
 // zero units stays in whole polynomials of their own and is never added to `partial`.
-// LDS: that of the transforms (the packed chunk lies behind the int32 image in the wave's region, as in records_decode).
+// LDS: that of the transforms (wave_lds: the packed chunk lies behind the int32 image in the wave's region).
 template <int LOGD, bool FAST>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void aggregate_encoded(const uint8_t *in, const int32_t *__restrict__ alpha,
                                                                          const int *__restrict__ skip, unsigned n, unsigned rec_values,
                                                                          unsigned rec_bytes, int w, int bound, unsigned long long *partial,
                                                                          const double2 *__restrict__ twB, const FzTwA *tab, FzMod m) {
     using G = Geom<LOGD>;
-    constexpr int D = G::D, L = G::L, PPW = G::PPW, NE = G::NE, PS = G::PS;
-    constexpr int REGION = PPW * PS;
-    static_assert(REGION == 18 * 64, "a lane's 16 sums and their pad are a wave's region");
+    constexpr int D = G::D, L = G::L, REGION = G::PPW * G::PS;
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int p = lane / L, r = lane % L;
     const unsigned col = blockIdx.x;
@@ -84,12 +81,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void aggregate_encoded(const u
     const bool any = cur < hi;
     Packed raw0 = {};
     if (any) raw0 = packed_load(in + (size_t)cur * rec_bytes, col, rec_bytes, w, lane);      // before the table: see fwd16_run
-    for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
-    __syncthreads();
-    double *region = lds + wave * REGION;
-    int32_t *stage = reinterpret_cast<int32_t *>(region);
-    uint8_t *pk = reinterpret_cast<uint8_t *>(region) + kPackOff;
-    double *row = region + p * PS;
+    const double2 *s_tw = twiddles_to_lds<LOGD>(lds, twB);
+    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
     double acc[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.0;
@@ -113,42 +106,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void aggregate_encoded(const u
         if (more) raw = packed_load(in + (size_t)nxt * rec_bytes, col, rec_bytes, w, lane);
         wave_sync();
         uint32_t u[16];
-        int wl = w;
-        asm volatile("" : "+s"(wl));                      // see records_encode
-        fields_unpack(reinterpret_cast<const uint16_t *>(pk) + lane * wl, u, wl);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int4 t;                                       // u - B: the low 32 bits are z whenever u <= 2B
-            t.x = (int)(u[4 * k + 0] - bnd);
-            t.y = (int)(u[4 * k + 1] - bnd);
-            t.z = (int)(u[4 * k + 2] - bnd);
-            t.w = (int)(u[4 * k + 3] - bnd);
-            *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = t;
-        }
+        fields_to_image(W.pk, W.stage, w, bnd, lane, u);  // no range test here: the skip words carry its outcome
         wave_sync();
         double a[16];
-        {
-            int x[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) x[k] = stage[pad4(p * D + r + L * k)];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) a[k] = (double)x[k];
-        }
-        wave_sync();
-        TabPtr t = (TabPtr)tab;
-        asm volatile("" : "+s"(t));
-        fwd16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
-        // lane (p, r) holds outputs 16r .. 16r + 15 of polynomial p, not reduced (|a| < 2^38); alpha_hat is any int32:
-        // |a * alpha| < 2^69 is inside fz_mulmod's bound, its result within 2^18 of q/2, and fz_cent makes it canonical
-        const int av[16] = {al[0].x, al[0].y, al[0].z, al[0].w, al[1].x, al[1].y, al[1].z, al[1].w,
-                            al[2].x, al[2].y, al[2].z, al[2].w, al[3].x, al[3].y, al[3].z, al[3].w};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc[k] += fz_cent(fz_mulmod(a[k], (double)av[k], m), m);
-        if (more) packed_to_lds(pk, raw, w, lane);        // waits for the prefetched chunk (the passes are done with the region)
+        image_fwd16<LOGD, FAST>(W.stage, a, W.row, p, r, s_tw, tab, m);
+        mulacc16(acc, a, al, m);                          // lane (p, r): outputs 16r .. 16r + 15 of polynomial p by alpha_hat_i[16r ..]
+        if (more) packed_to_lds(W.pk, raw, w, lane);      // waits for the prefetched chunk (the passes are done with the region)
         return after;
     };
     if (any) {
-        packed_to_lds(pk, raw0, w, lane);
+        packed_to_lds(W.pk, raw0, w, lane);
         unsigned nxt = next_ok(cur + kWavesPerBlock);
         while (nxt < hi) {
             const int after = iteration(cur, nxt, std::true_type());
@@ -159,11 +126,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void aggregate_encoded(const u
         iteration(cur, cur, std::false_type());
     }
     // the four waves' sums meet in LDS: lane's 16 at doubles 18 * lane .. (element e = 16 * lane + k of the chunk at pad16(e))
-    {
-        double2 *blk = reinterpret_cast<double2 *>(region + 18 * lane);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) blk[k] = make_double2(acc[2 * k], acc[2 * k + 1]);
-    }
+    sums_to_lds(W.region, acc, lane);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < kChunk / (64 * kWavesPerBlock); ++j) {
@@ -176,8 +139,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void aggregate_encoded(const u
 }
 
 template <int LOGD, bool FAST>
-int launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, unsigned rv, int w,
-                             int bound, int64_t *partial) {
+int launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, unsigned rv, unsigned rb,
+                             int w, int bound, int64_t *partial) {
     // columns x slices ~ the resident grid, and no more slices than give every wave of a workgroup a signer
     const size_t columns = (rv + kChunk - 1) / kChunk, per_wg = (n + kWavesPerBlock - 1) / kWavesPerBlock;
     size_t slices = (size_t)ctx->grid_aggenc / columns;
@@ -185,7 +148,7 @@ int launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *a
     slices = slices < per_wg ? slices : per_wg;
     slices = slices < 65535 ? slices : 65535;
     hipLaunchKernelGGL((aggregate_encoded<LOGD, FAST>), dim3((unsigned)columns, (unsigned)slices), dim3(64 * kWavesPerBlock), 0, ctx->stream,
-                       bytes, alpha, skip, (unsigned)n, rv, (unsigned)((size_t)rv / 8 * (size_t)w), w, bound, (unsigned long long *)partial,
+                       bytes, alpha, skip, (unsigned)n, rv, rb, w, bound, (unsigned long long *)partial,
                        (const double2 *)ctx->d_twB, (const FzTwA *)ctx->d_twAB, ctx->mod);
     return FZ_OK;
 }
@@ -222,11 +185,11 @@ int fz_launch_check_records(fz_ctx *ctx, const uint8_t *bytes, size_t n, int row
 // 16-byte aligned.
 int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, int l, int w,
                                 int64_t bound, int64_t *d_partial, int32_t *d_out) {
-    const unsigned rv = (unsigned)l * (unsigned)ctx->degree;
+    const unsigned rv = (unsigned)l * (unsigned)ctx->degree, rb = (unsigned)fz_record_bytes(ctx->degree, l, w);
     int rc = fz_check_hip(hipMemsetAsync(d_partial, 0, (size_t)rv * sizeof(int64_t), ctx->stream), "aggregate partial clear");
     if (rc != FZ_OK) return rc;
     rc = fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
-        return launch_aggregate_encoded<logd(), fast()>(ctx, bytes, alpha, skip, n, rv, w, (int)bound, d_partial);
+        return launch_aggregate_encoded<logd(), fast()>(ctx, bytes, alpha, skip, n, rv, rb, w, (int)bound, d_partial);
     });
     if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "aggregate_encoded launch");
     if (rc != FZ_OK || d_out == nullptr) return rc;

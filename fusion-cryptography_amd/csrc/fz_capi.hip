@@ -387,13 +387,15 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
 }
 
-// compact byte encoding: the checks both directions share; *w = bit_length(2 * bound)
-static int records_args(fz_ctx *ctx, const void *src, const void *dst, size_t n, int rows, int64_t bound, const int *d_status, int *w) {
+// compact byte encoding: the checks of all five entries, in the order that decides the return code when more than one thing is
+// wrong: context, rows and bound; n == 0 is FZ_OK from here on; the entry's pointers (`ptrs_wrong`: what is wrong with them, NULL
+// when nothing is -- which pointers an entry takes and how they must be aligned is its own business); degree; size.
+// -> *w = bit_length(2 * bound).  Conditions of an entry that hold whatever n is come before this call, its own limits after it.
+static int records_args(fz_ctx *ctx, size_t n, int rows, int64_t bound, const char *ptrs_wrong, int *w) {
     FZ_REQUIRE(ctx && rows >= 1, "bad argument");
     FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "bound %lld outside [1, (q-1)/2]", (long long)bound);
     if (n == 0) return FZ_OK;
-    FZ_REQUIRE(src && dst && d_status, "NULL argument");
-    FZ_REQUIRE((((uintptr_t)src | (uintptr_t)dst | (uintptr_t)d_status) & 15) == 0, "rows, bytes and status must be 16-byte aligned");
+    FZ_REQUIRE(!ptrs_wrong, "%s", ptrs_wrong);
     if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
     FZ_REQUIRE((uint64_t)rows * (uint64_t)ctx->degree <= 0x7fffffffull && n <= ((size_t)-1 >> 3) / ((size_t)rows * ctx->degree),
                "%zu records of %d rows are too many", n, rows);
@@ -403,10 +405,23 @@ static int records_args(fz_ctx *ctx, const void *src, const void *dst, size_t n,
     return FZ_OK;
 }
 
+// the three buffers of an entry that wants all of them 16-byte aligned
+static const char *records_ptrs(const void *a, const void *b, const void *c) {
+    if (!a || !b || !c) return "NULL argument";
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) != 0 ? "buffers must be 16-byte aligned" : nullptr;
+}
+
+// the consumers that walk ONE record's chunks (blockIdx names the record): every record must begin on a 16-byte unit
+static int records_whole_units(const fz_ctx *ctx, int rows, int w) {
+    const size_t rb = fz_record_bytes(ctx->degree, rows, w);
+    if (rb % 16 != 0) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: reading them record by record needs a multiple of 16", rb);
+    return FZ_OK;
+}
+
 int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n, int rows, int coef, int64_t bound, uint8_t *d_bytes,
                             int *d_status) {
     int w = 0;
-    FZ_TRY(records_args(ctx, d_rows, d_bytes, n, rows, bound, d_status, &w));
+    FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_rows, d_bytes, d_status), &w));
     if (n == 0) return FZ_OK;
     FZ_DEV(ctx);
     return fz_launch_records(ctx, false, d_rows, d_bytes, n, rows, coef != 0, w, bound, d_status);
@@ -415,7 +430,7 @@ int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n, int ro
 int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int coef, int64_t bound, int32_t *d_rows,
                             int *d_status) {
     int w = 0;
-    FZ_TRY(records_args(ctx, d_bytes, d_rows, n, rows, bound, d_status, &w));
+    FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_bytes, d_rows, d_status), &w));
     if (n == 0) return FZ_OK;
     FZ_DEV(ctx);
     return fz_launch_records(ctx, true, d_bytes, d_rows, n, rows, coef != 0, w, bound, d_status);
@@ -423,7 +438,7 @@ int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int r
 
 int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status) {
     int w = 0;
-    FZ_TRY(records_args(ctx, d_bytes, d_bytes, n, rows, bound, d_status, &w));
+    FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_bytes, d_bytes, d_status), &w));
     if (n == 0) return FZ_OK;
     FZ_DEV(ctx);
     return fz_launch_check_records(ctx, d_bytes, n, rows, w, bound, d_status);
@@ -434,11 +449,9 @@ int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_
     int w = 0;
     FZ_REQUIRE(N == 0 || d_alpha_hat, "NULL argument");
     FZ_REQUIRE((((uintptr_t)d_alpha_hat | (uintptr_t)d_out) & 15) == 0, "alpha_hat and the aggregate must be 16-byte aligned");
-    FZ_TRY(records_args(ctx, d_bytes, d_partial, N, l, bound, (const int *)d_alpha_hat, &w));
+    FZ_TRY(records_args(ctx, N, l, bound, records_ptrs(d_bytes, d_partial, d_alpha_hat), &w));
     if (N == 0) return FZ_OK;
-    if (((size_t)l * ctx->degree / 8 * (size_t)w) % 16 != 0)
-        return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: the aggregation from bytes needs a multiple of 16",
-                            (size_t)l * ctx->degree / 8 * (size_t)w);
+    FZ_TRY(records_whole_units(ctx, l, w));
     if (N >= ((size_t)1 << 22))
         return fz_set_error(FZ_E_UNSUPPORTED, "N=%zu too large for exact fp64 accumulation (< 2^22)", N);
     FZ_DEV(ctx);
@@ -447,22 +460,18 @@ int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_
 
 int fz_verify_encoded_async(fz_ctx *ctx, const int32_t *d_A, const uint8_t *d_bytes, size_t N, int l, int64_t bound,
                             const int32_t *d_target, const int32_t *d_vk, const int32_t *d_c_hat, int *d_verdicts) {
-    FZ_REQUIRE(ctx && l >= 1, "bad argument");
-    FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "bound %lld outside [1, (q-1)/2]", (long long)bound);
+    int w = 0;
     FZ_REQUIRE((d_target != nullptr) != (d_vk != nullptr || d_c_hat != nullptr) && (d_vk != nullptr) == (d_c_hat != nullptr),
                "exactly one of d_target, or the pair d_vk and d_c_hat, must be given");
+    const char *ptrs_wrong = nullptr;
+    if (!d_A || !d_bytes || !d_verdicts) ptrs_wrong = "NULL argument";
+    else if ((((uintptr_t)d_bytes | (uintptr_t)d_A) & 15) != 0) ptrs_wrong = "the bytes and A must be 16-byte aligned";
+    else if ((((uintptr_t)d_target | (uintptr_t)d_vk | (uintptr_t)d_c_hat | (uintptr_t)d_verdicts) & 3) != 0)
+        ptrs_wrong = "target, keys, challenges and verdicts must be 4-byte aligned";
+    FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
     if (N == 0) return FZ_OK;
-    FZ_REQUIRE(d_A && d_bytes && d_verdicts, "NULL argument");
-    FZ_REQUIRE((((uintptr_t)d_bytes | (uintptr_t)d_A) & 15) == 0, "the bytes and A must be 16-byte aligned");
-    FZ_REQUIRE((((uintptr_t)d_target | (uintptr_t)d_vk | (uintptr_t)d_c_hat | (uintptr_t)d_verdicts) & 3) == 0,
-               "target, keys, challenges and verdicts must be 4-byte aligned");
-    if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
-    FZ_REQUIRE((uint64_t)l * (uint64_t)ctx->degree <= 0x7fffffffull && N <= ((size_t)-1 >> 3) / ((size_t)l * ctx->degree),
-               "%zu records of %d rows are too many", N, l);
-    int w = 0;
-    while ((2 * bound) >> w) ++w;
-    const size_t rb = (size_t)l * ctx->degree / 8 * (size_t)w;
-    if (rb % 16 != 0) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: the verification from bytes needs a multiple of 16", rb);
+    FZ_TRY(records_whole_units(ctx, l, w));
+    const size_t rb = fz_record_bytes(ctx->degree, l, w);
     if (rb > 0xffffffffull) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes are too long", rb);
     FZ_DEV(ctx);
     return fz_launch_verify_encoded(ctx, d_A, d_bytes, N, l, w, bound, d_target, d_vk, d_c_hat, d_verdicts);

@@ -269,6 +269,8 @@ bool fz_polymul16_ok(const fz_ctx *ctx, const int32_t *f, const int32_t *g, cons
 
 // compact byte encoding (fz_records.hip; degree 64 / 256): n records of rows * degree values, w-bit fields u = z + bound; encode (decode =
 // false) rows -> bytes, decode bytes -> rows; d_status [n] cleared, then 0 or FZ_VERDICT_NORM / FZ_VERDICT_ENCODING; failed records zeroed
+// bytes of ONE record: rows * degree fields of w bits (the degree is a multiple of 8)
+static inline size_t fz_record_bytes(int degree, int rows, int w) { return (size_t)rows * (size_t)degree / 8 * (size_t)w; }
 int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
                       int *d_status);
 int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_rec (fz_ntt_query_grid calls it)

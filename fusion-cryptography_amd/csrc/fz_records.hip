@@ -49,11 +49,8 @@ template <int LOGD, bool FAST, bool COEF>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int32_t *in, uint8_t *out, size_t total, unsigned rec_values,
                                                                       int w, int bound, int *status, const double2 *__restrict__ itwB,
                                                                       const FzTwA *tab, FzMod m) {
-    using G = Geom<LOGD>;
-    constexpr int D = G::D, L = G::L, PPW = G::PPW, NE = G::NE, PS = G::PS;
-    constexpr int REGION = PPW * PS;
+    constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int p = lane / L, r = lane % L;
     const size_t tasks = (total + kChunk - 1) / kChunk;
@@ -61,16 +58,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int3
     const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
     Chunk raw0 = {};
     if (first < tasks) raw0 = chunk_load(in, first, total, lane);      // before the table: see fwd16_run
-    if constexpr (COEF) {
-        for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = itwB[i];
-        __syncthreads();
-    }
-    double *region = lds + wave * REGION;
-    int32_t *stage = reinterpret_cast<int32_t *>(region);
-    uint8_t *pk = reinterpret_cast<uint8_t *>(region) + kPackOff;
-    double *row = region + p * PS;
+    const double2 *s_tw = nullptr;
+    if constexpr (COEF) s_tw = twiddles_to_lds<LOGD>(lds, itwB);
+    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
     if (first >= tasks) return;
-    chunk_to_lds(stage, lane, raw0);
+    chunk_to_lds(W.stage, lane, raw0);
     RecWalk walk(first, stride, rec_values, lane);
     unsigned two_b = 2u * (unsigned)bound, wmask = (unsigned)((1ull << w) - 1), bnd = (unsigned)bound;
     asm volatile("" : "+v"(two_b), "+v"(wmask), "+v"(bnd));       // VALU operands only (see RecWalk)
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int3
             double a[16];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int4 t = *reinterpret_cast<const int4 *>(stage + pad4(16 * lane + 4 * k));
+                const int4 t = *reinterpret_cast<const int4 *>(W.stage + pad4(16 * lane + 4 * k));
                 a[4 * k + 0] = (double)t.x;
                 a[4 * k + 1] = (double)t.y;
                 a[4 * k + 2] = (double)t.z;
@@ -96,9 +88,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int3
             wave_sync();
             TabPtr t = (TabPtr)tab;
             asm volatile("" : "+s"(t));
-            inv16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
+            inv16_passes<LOGD, FAST>(a, W.row, r, s_tw, t[0], m);
 #pragma unroll
-            for (int k = 0; k < 16; ++k) stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
+            for (int k = 0; k < 16; ++k) W.stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
             wave_sync();
         }
         // the lane's 16 consecutive values: centred (the transform's outputs already are), range-checked, packed
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int3
         uint32_t u[16], hi = 0, mx = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int4 t = *reinterpret_cast<const int4 *>(stage + pad4(16 * lane + 4 * k));
+            const int4 t = *reinterpret_cast<const int4 *>(W.stage + pad4(16 * lane + 4 * k));
             const int v[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -118,11 +110,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int3
             }
         }
         const bool bad = hi != 0 || mx > two_b;
-        fields_pack(reinterpret_cast<uint16_t *>(pk) + lane * wl, u, wl);
+        fields_pack(reinterpret_cast<uint16_t *>(W.pk) + lane * wl, u, wl);
         wave_sync();
-        const Packed o = packed_from_lds(pk, wl, lane);
+        const Packed o = packed_from_lds(W.pk, wl, lane);
         wave_sync();
-        if (more) chunk_to_lds(stage, lane, raw);         // waits for the prefetched loads (no store is younger)
+        if (more) chunk_to_lds(W.stage, lane, raw);       // waits for the prefetched loads (no store is younger)
         packed_store(out, task, total_bytes, wl, lane, o);
         const bool valid = task * kChunk + 16 * lane < total;
         records_flag(status, walk.rec, bad && valid, FZ_VERDICT_NORM, lane);
@@ -139,11 +131,8 @@ template <int LOGD, bool FAST, bool COEF>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void records_decode(const uint8_t *in, int32_t *out, size_t total, unsigned rec_values,
                                                                       int w, int bound, int *status, const double2 *__restrict__ twB,
                                                                       const FzTwA *tab, FzMod m) {
-    using G = Geom<LOGD>;
-    constexpr int D = G::D, L = G::L, PPW = G::PPW, NE = G::NE, PS = G::PS;
-    constexpr int REGION = PPW * PS;
+    constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int p = lane / L, r = lane % L;
     const size_t tasks = (total + kChunk - 1) / kChunk;
@@ -152,16 +141,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_decode(const uint
     const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
     Packed raw0 = {};
     if (first < tasks) raw0 = packed_load(in, first, total_bytes, w, lane);
-    if constexpr (COEF) {
-        for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
-        __syncthreads();
-    }
-    double *region = lds + wave * REGION;
-    int32_t *stage = reinterpret_cast<int32_t *>(region);
-    uint8_t *pk = reinterpret_cast<uint8_t *>(region) + kPackOff;
-    double *row = region + p * PS;
+    const double2 *s_tw = nullptr;
+    if constexpr (COEF) s_tw = twiddles_to_lds<LOGD>(lds, twB);
+    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
     if (first >= tasks) return;
-    packed_to_lds(pk, raw0, w, lane);
+    packed_to_lds(W.pk, raw0, w, lane);
     RecWalk walk(first, stride, rec_values, lane);
     const uint32_t two_b = 2u * (unsigned)bound;
 
@@ -170,35 +154,22 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_decode(const uint
         Packed raw = {};
         if (more) raw = packed_load(in, task + stride, total_bytes, w, lane);
         wave_sync();
-        uint32_t u[16], mx = 0;
-        int wl = w;
-        asm volatile("" : "+s"(wl));                      // see records_encode
-        fields_unpack(reinterpret_cast<const uint16_t *>(pk) + lane * wl, u, wl);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int4 t;                                       // u - B: the low 32 bits are z whenever u <= 2B
-            t.x = (int)(u[4 * k + 0] - (uint32_t)bound);
-            t.y = (int)(u[4 * k + 1] - (uint32_t)bound);
-            t.z = (int)(u[4 * k + 2] - (uint32_t)bound);
-            t.w = (int)(u[4 * k + 3] - (uint32_t)bound);
-            mx = max(max(mx, max(u[4 * k + 0], u[4 * k + 1])), max(u[4 * k + 2], u[4 * k + 3]));
-            *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = t;
-        }
-        const bool bad = mx > two_b;
+        uint32_t u[16];
+        const bool bad = fields_to_image(W.pk, W.stage, w, (uint32_t)bound, lane, u) > two_b;
         wave_sync();
         if constexpr (COEF) {
             double a[16];
-            {
-                int x[16];
+            {                                             // image_fwd16's text, kept here: its call changes this kernel's schedule
+                int x[16];                                // (docs/HISTORY.md section M)
 #pragma unroll
-                for (int k = 0; k < 16; ++k) x[k] = stage[pad4(p * D + r + L * k)];
+                for (int k = 0; k < 16; ++k) x[k] = W.stage[pad4(p * D + r + L * k)];
 #pragma unroll
                 for (int k = 0; k < 16; ++k) a[k] = (double)x[k];
             }
             wave_sync();
             TabPtr t = (TabPtr)tab;
             asm volatile("" : "+s"(t));
-            fwd16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
+            fwd16_passes<LOGD, FAST>(a, W.row, r, s_tw, t[0], m);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 int4 o;
@@ -206,16 +177,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_decode(const uint
                 o.y = (int)fz_cent(a[4 * k + 1], m);
                 o.z = (int)fz_cent(a[4 * k + 2], m);
                 o.w = (int)fz_cent(a[4 * k + 3], m);
-                *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = o;
+                *reinterpret_cast<int4 *>(W.stage + pad4(16 * lane + 4 * k)) = o;
             }
             wave_sync();
         }
-        const int4 o0 = *reinterpret_cast<const int4 *>(stage + pad4(4 * lane));
-        const int4 o1 = *reinterpret_cast<const int4 *>(stage + pad4(256 + 4 * lane));
-        const int4 o2 = *reinterpret_cast<const int4 *>(stage + pad4(512 + 4 * lane));
-        const int4 o3 = *reinterpret_cast<const int4 *>(stage + pad4(768 + 4 * lane));
+        const int4 o0 = *reinterpret_cast<const int4 *>(W.stage + pad4(4 * lane));
+        const int4 o1 = *reinterpret_cast<const int4 *>(W.stage + pad4(256 + 4 * lane));
+        const int4 o2 = *reinterpret_cast<const int4 *>(W.stage + pad4(512 + 4 * lane));
+        const int4 o3 = *reinterpret_cast<const int4 *>(W.stage + pad4(768 + 4 * lane));
         wave_sync();
-        if (more) packed_to_lds(pk, raw, w, lane);        // waits for the prefetched loads (no store is younger)
+        if (more) packed_to_lds(W.pk, raw, w, lane);      // waits for the prefetched loads (no store is younger)
         chunk_store(out, task, total, lane, o0, o1, o2, o3);
         const bool valid = task * kChunk + 16 * lane < total;
         records_flag(status, walk.rec, bad && valid, FZ_VERDICT_ENCODING, lane);
@@ -287,7 +258,7 @@ int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size
         });
     if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "records launch");
     if (rc != FZ_OK) return rc;
-    const size_t rec_bytes = decode ? (size_t)rv * sizeof(int32_t) : (size_t)rv / 8 * (size_t)w;
+    const size_t rec_bytes = decode ? (size_t)rv * sizeof(int32_t) : fz_record_bytes(ctx->degree, rows, w);
     const size_t zcap = (size_t)ctx->num_cu * 4;
     hipLaunchKernelGGL(records_zero_failed, dim3((unsigned)(n < zcap ? n : zcap)), dim3(256), 0, ctx->stream, (const int *)d_status, n,
                        (uint8_t *)dst, rec_bytes);

@@ -1,7 +1,8 @@
 // fz_records_dev.h -- the device building blocks of the compact byte encoding that more than one unit uses (fz_records.hip: the
-// records_* kernels; fz_aggregate_encoded.hip: the range check and the aggregation straight from the bytes): the packed chunk of
-// the chunk walk, the field unpacking, the per-record status flag and the record walk.  No kernels and no host code here;
-// everything is private to the unit that includes it.
+// records_* kernels; fz_aggregate_encoded.hip: the range check and the aggregation straight from the bytes; fz_verify_encoded.hip:
+// the verification straight from the bytes): the packed chunk of the chunk walk, the field unpacking, the steps from the packed
+// chunk to the transform's outputs and their sums, the per-record status flag and the record walk.  No kernels and no host code
+// here; everything is private to the unit that includes it.
 #ifndef FZ_RECORDS_DEV_H
 #define FZ_RECORDS_DEV_H
 
@@ -89,6 +90,98 @@ __device__ __forceinline__ void fields_unpack(const uint16_t *src, uint32_t (&u)
         acc >>= w;
         nb -= w;
     }
+}
+
+// The steps every consumer of the bytes takes between its prefetch and its own work on the transform's outputs.  `pk`, `stage`
+// and `row` are the packed chunk, the int32 image and the lane's polynomial p in the wave's region; (p, r) = (lane / L, lane % L).
+
+// the lane's w words of the packed chunk -> its 16 fields, in u and as u - B in the int32 image (chunk_to_lds' layout: the low 32
+// bits are z whenever u <= 2B, just an integer otherwise); -> the lane's largest field, for the range test u <= 2B of those who
+// make it.  What depends on w alone (the bit offsets of the unpacking) is recomputed per chunk, not held across the loop: w is
+// pinned in a scalar register here, as records_encode pins it for the packing.
+// The form is the one that leaves every caller's code as it was with the text in place (docs/HISTORY.md section M): arguments
+// by reference, as a kernel's iteration lambda holds them, and the fields in an array of the caller's.
+__device__ __forceinline__ uint32_t fields_to_image(const uint8_t *const &pk, int32_t *const &stage, const int &w, const uint32_t &bound,
+                                                    const int &lane, uint32_t (&u)[16]) {
+    uint32_t mx = 0;
+    int wl = w;
+    asm volatile("" : "+s"(wl));
+    fields_unpack(reinterpret_cast<const uint16_t *>(pk) + lane * wl, u, wl);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int4 t;
+        t.x = (int)(u[4 * k + 0] - bound);
+        t.y = (int)(u[4 * k + 1] - bound);
+        t.z = (int)(u[4 * k + 2] - bound);
+        t.w = (int)(u[4 * k + 3] - bound);
+        mx = max(max(mx, max(u[4 * k + 0], u[4 * k + 1])), max(u[4 * k + 2], u[4 * k + 3]));
+        *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = t;
+    }
+    return mx;
+}
+
+// the image (complete: the caller's wave_sync lies behind its last write) read transposed, a[k] = element r + L * k of polynomial
+// p, and the forward passes on it: -> a[k] = output 16 r + k of polynomial p, not reduced (|a| < 2^38).  The wave-uniform table
+// is taken from constant memory here, its pointer pinned in scalar registers (TabPtr).  The image is free once this returns.
+template <int LOGD, bool FAST>
+__device__ __forceinline__ void image_fwd16(const int32_t *stage, double (&a)[16], double *row, int p, int r, const double2 *s_tw,
+                                            const FzTwA *tab, const FzMod &m) {
+    constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
+    {
+        int x[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = stage[pad4(p * D + r + L * k)];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) a[k] = (double)x[k];
+    }
+    wave_sync();
+    TabPtr t = (TabPtr)tab;
+    asm volatile("" : "+s"(t));
+    fwd16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
+}
+
+// acc[k] += cent(a[k] * x[k]) for the 16 outputs image_fwd16 leaves and the 16 multipliers x = al[0].x .. al[3].w.  The
+// multipliers are any int32: |a * x| < 2^69 is inside fz_mulmod's bound, its result within 2^18 of q/2, and fz_cent makes it
+// canonical, |p| <= (q-1)/2 < 2^31 -- so fp64 sums of fewer than 2^22 of them are exact.
+__device__ __forceinline__ void mulacc16(double (&acc)[16], const double (&a)[16], const int4 (&al)[4], const FzMod &m) {
+    const int x[16] = {al[0].x, al[0].y, al[0].z, al[0].w, al[1].x, al[1].y, al[1].z, al[1].w,
+                       al[2].x, al[2].y, al[2].z, al[2].w, al[3].x, al[3].y, al[3].z, al[3].w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] += fz_cent(fz_mulmod(a[k], (double)x[k], m), m);
+}
+
+// a lane's 16 sums to LDS, where a workgroup's waves meet: doubles 18 * lane .. 18 * lane + 15 of the wave's region, i.e. element
+// e = 16 * lane + k of the chunk at pad16(e), coefficient i of the wave's polynomial q at q * PS + pad16(i); the two pad doubles
+// behind them are left alone
+static_assert(Geom<6>::PPW * Geom<6>::PS == 18 * 64 && Geom<8>::PPW * Geom<8>::PS == 18 * 64,
+              "a lane's 16 sums and their pad are a wave's region");
+__device__ __forceinline__ void sums_to_lds(double *region, const double (&acc)[16], int lane) {
+    double2 *blk = reinterpret_cast<double2 *>(region + 18 * lane);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) blk[k] = make_double2(acc[2 * k], acc[2 * k + 1]);
+}
+
+// A kernel's opening on the transforms' LDS (lds16_doubles<LOGD>() doubles: a region per wave, then the per-lane twiddle table):
+// the table copied in behind a workgroup barrier, and the wave's region with the pieces the steps above work on
+template <int LOGD>
+__device__ __forceinline__ const double2 *twiddles_to_lds(double *lds, const double2 *__restrict__ twB) {
+    using G = Geom<LOGD>;
+    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * G::PPW * G::PS);
+    for (int i = threadIdx.x; i < G::NE * G::L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
+    __syncthreads();
+    return s_tw;
+}
+struct WaveLds {
+    double *region;      // the wave's transpose region
+    int32_t *stage;      // the int32 image at its start
+    uint8_t *pk;         // the packed chunk behind the image
+    double *row;         // the transpose buffer of the lane's polynomial p
+};
+template <int LOGD>
+__device__ __forceinline__ WaveLds wave_lds(double *lds, int wave, int p) {
+    using G = Geom<LOGD>;
+    double *region = lds + wave * G::PPW * G::PS;
+    return {region, reinterpret_cast<int32_t *>(region), reinterpret_cast<uint8_t *>(region) + kPackOff, region + p * G::PS};
 }
 
 // Per-record status: every (wave, record) with a failing lane sets its record's word with ONE atomic (at most 16 records meet

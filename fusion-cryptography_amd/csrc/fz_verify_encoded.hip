@@ -37,7 +37,7 @@ __device__ __forceinline__ int venc_want(const int32_t *target, const int32_t *v
 // and shared by all records).
 // Exactness: every product is made canonical, |p| <= (q-1)/2 < 2^31, and a record adds l of them per coefficient: the fp64 sums
 // (per lane, then over the PPW slots and the four waves in LDS) stay below 2^53 for l < 2^22; the launcher refuses larger l.
-// A is any int32: |a| < 2^38 after the passes, |a * A| < 2^69 is inside fz_mulmod's bound, as in aggregate_encoded.
+// A is any int32: the bounds of the product are mulacc16's (fz_records_dev.h).
 // A non-canonical record cannot fault: u - B is just an integer (its low 32 bits), and nothing is indexed by it.
 // Slots of a tail chunk past row l - 1 read no bytes (packed_load stops at the record's length), read no A, raise no range
 // flag and are not accumulated.
@@ -45,9 +45,9 @@ __device__ __forceinline__ int venc_want(const int32_t *target, const int32_t *v
 // touched.  R > 1: the workgroup adds its D sums to the record's slot of `share` with 64-bit integer atomics (exact and
 // commutative: the order of arrival cannot change a bit) and ORs its range flag into the slot's status word; the caller cleared
 // the slots before this launch and runs verify_encoded_finish after it -- stream order is the only ordering relied upon.
-// LDS: that of the transforms, not a word more (the packed chunk lies behind the int32 image in the wave's region, as in
-// records_decode; the workgroup's flags are the pad words of lane 0's sums in every wave's region, one range flag and one
-// mismatch flag per wave, OR-ed by whoever reads them after a barrier).
+// LDS: that of the transforms, not a word more (wave_lds: the packed chunk lies behind the int32 image in the wave's region;
+// the workgroup's flags are the pad words of lane 0's sums in every wave's region, one range flag and one mismatch flag per
+// wave, OR-ed by whoever reads them after a barrier).
 template <int LOGD, bool FAST>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void verify_encoded(const uint8_t *in, const int32_t *__restrict__ A, unsigned rec_values,
                                                                       unsigned rec_bytes, int l, int w, int bound,
@@ -55,12 +55,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void verify_encoded(const uint
                                                                       const int32_t *__restrict__ chal, unsigned long long *share,
                                                                       int *verdict, const double2 *__restrict__ twB, const FzTwA *tab, FzMod m) {
     using G = Geom<LOGD>;
-    constexpr int D = G::D, L = G::L, PPW = G::PPW, NE = G::NE, PS = G::PS;
-    constexpr int REGION = PPW * PS;
-    static_assert(REGION == 18 * 64, "a lane's 16 sums and their pad are a wave's region");
+    constexpr int D = G::D, L = G::L, PPW = G::PPW, PS = G::PS, REGION = PPW * PS;
     static_assert(D <= 64 * kWavesPerBlock, "one thread per coefficient in the combine step");
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    double2 *s_tw = reinterpret_cast<double2 *>(lds + kWavesPerBlock * REGION);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int p = lane / L, r = lane % L;
     const unsigned R = gridDim.x;
@@ -75,12 +72,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void verify_encoded(const uint
     // overlap; the centred target waits in ONE register across the row loop
     int want = 0;
     if (R == 1 && threadIdx.x < D) want = venc_want<D>(target, vk, chal, g, threadIdx.x, m);
-    for (int i = threadIdx.x; i < NE * L; i += 64 * kWavesPerBlock) s_tw[i] = twB[i];
-    __syncthreads();
-    double *region = lds + wave * REGION;
-    int32_t *stage = reinterpret_cast<int32_t *>(region);
-    uint8_t *pk = reinterpret_cast<uint8_t *>(region) + kPackOff;
-    double *row = region + p * PS;
+    const double2 *s_tw = twiddles_to_lds<LOGD>(lds, twB);
+    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
     double acc[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.0;
@@ -103,47 +96,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void verify_encoded(const uint
         Packed raw = {};
         if (more) raw = packed_load(in, c + stride, rec_bytes, w, lane);
         wave_sync();
-        uint32_t u[16], mx = 0;
-        int wl = w;
-        asm volatile("" : "+s"(wl));                      // see records_encode
-        fields_unpack(reinterpret_cast<const uint16_t *>(pk) + lane * wl, u, wl);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            int4 t;                                       // u - B: the low 32 bits are z whenever u <= 2B
-            t.x = (int)(u[4 * k + 0] - bnd);
-            t.y = (int)(u[4 * k + 1] - bnd);
-            t.z = (int)(u[4 * k + 2] - bnd);
-            t.w = (int)(u[4 * k + 3] - bnd);
-            mx = max(max(mx, max(u[4 * k + 0], u[4 * k + 1])), max(u[4 * k + 2], u[4 * k + 3]));
-            *reinterpret_cast<int4 *>(stage + pad4(16 * lane + 4 * k)) = t;
-        }
+        uint32_t u[16];
+        const uint32_t mx = fields_to_image(W.pk, W.stage, w, bnd, lane, u);
         // the lane's 16 fields are values c * 1024 + 16 lane .. of the record: past its end they are the zero units, not fields
         bad |= __ballot(mx > two_b && c * (unsigned)kChunk + 16u * lane < rv) != 0;       // wave-uniform
         wave_sync();
         double a[16];
-        {
-            int x[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) x[k] = stage[pad4(p * D + r + L * k)];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) a[k] = (double)x[k];
-        }
-        wave_sync();
-        TabPtr t = (TabPtr)tab;
-        asm volatile("" : "+s"(t));
-        fwd16_passes<LOGD, FAST>(a, row, r, s_tw, t[0], m);
-        // lane (p, r) holds outputs 16r .. 16r + 15 of row c * PPW + p, not reduced (|a| < 2^38); A is any int32:
-        // |a * A| < 2^69 is inside fz_mulmod's bound, its result within 2^18 of q/2, and fz_cent makes it canonical
+        image_fwd16<LOGD, FAST>(W.stage, a, W.row, p, r, s_tw, tab, m);
+        // lane (p, r): outputs 16r .. 16r + 15 of row c * PPW + p by A[row][16r ..].  mulacc16's text, kept here: beside the other
+        // helpers its call makes the compiler zero the 16 sums in another order in this kernel (docs/HISTORY.md section M)
         const int av[16] = {al[0].x, al[0].y, al[0].z, al[0].w, al[1].x, al[1].y, al[1].z, al[1].w,
                             al[2].x, al[2].y, al[2].z, al[2].w, al[3].x, al[3].y, al[3].z, al[3].w};
         if (live) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) acc[k] += fz_cent(fz_mulmod(a[k], (double)av[k], m), m);
         }
-        if (more) packed_to_lds(pk, raw, w, lane);        // waits for the prefetched chunk (the passes are done with the region)
+        if (more) packed_to_lds(W.pk, raw, w, lane);      // waits for the prefetched chunk (the passes are done with the region)
     };
     if (any) {
-        packed_to_lds(pk, raw0, w, lane);
+        packed_to_lds(W.pk, raw0, w, lane);
         unsigned c = first;
         for (; c + stride < chunks; c += stride) iteration(c, std::true_type());
         iteration(c, std::false_type());
@@ -151,12 +122,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void verify_encoded(const uint
     // the 16 sums of every lane meet in LDS over the PPW slots and the four waves: lane's 16 at doubles 18 * lane .. of its wave's
     // region, i.e. coefficient i of slot q at q * PS + pad16(i)
     wave_sync();
-    {
-        double2 *blk = reinterpret_cast<double2 *>(region + 18 * lane);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) blk[k] = make_double2(acc[2 * k], acc[2 * k + 1]);
-    }
-    if (lane == 0) region[16] = bad ? 1.0 : 0.0;         // the pad behind lane 0's sums: the wave's range flag
+    sums_to_lds(W.region, acc, lane);
+    if (lane == 0) W.region[16] = bad ? 1.0 : 0.0;       // the pad behind lane 0's sums: the wave's range flag
     __syncthreads();
     double sum = 0.0;
     if (threadIdx.x < D) {
@@ -169,7 +136,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void verify_encoded(const uint
     if (R == 1) {                                         // the whole record is this workgroup's: nothing to share
         const bool miss = threadIdx.x < D && (int)fz_cent_wide(sum, m) != want;
         const bool wave_miss = __ballot(miss) != 0;
-        if (lane == 0) region[17] = wave_miss ? 1.0 : 0.0;       // the other pad word: the wave's mismatch flag
+        if (lane == 0) W.region[17] = wave_miss ? 1.0 : 0.0;     // the other pad word: the wave's mismatch flag
         __syncthreads();
         if (threadIdx.x == 0) {
             bool wg_miss = false;
@@ -228,7 +195,7 @@ int fz_launch_verify_encoded(fz_ctx *ctx, const int32_t *A, const uint8_t *bytes
     if (rc != FZ_OK) return rc;
     if (ymax < 1) return fz_set_error(FZ_E_HIP, "max grid y reported as %d", ymax);
     const size_t D = (size_t)ctx->degree;
-    const unsigned rv = (unsigned)l * (unsigned)D, rb = (unsigned)((size_t)rv / 8 * (size_t)w);
+    const unsigned rv = (unsigned)l * (unsigned)D, rb = (unsigned)fz_record_bytes(ctx->degree, l, w);
     const size_t chunks = ((size_t)rv + kChunk - 1) / kChunk;
     size_t R = (chunks + kWavesPerBlock - 1) / kWavesPerBlock;
     const size_t fill = (size_t)ctx->num_cu * 2 / N;

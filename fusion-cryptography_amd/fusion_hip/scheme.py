@@ -316,13 +316,17 @@ class BatchScheme:
         vk = np.ascontiguousarray(vk.numpy() if isinstance(vk, DeviceArray) else vk, dtype=np.int32).reshape(-1, 2, self.d)
         return vk, np.ascontiguousarray(vk[:, 0]), np.ascontiguousarray(vk[:, 1])
 
-    def _challenges_both(self, vk, messages):
+    def _signer_count(self, vk):
+        return vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+
+    def _challenges_both(self, vk, messages, want_host=True):
         """hash_ch for every (key, message) in the CALLERS' order: -> (dC DeviceArray [N][d], c_hat host copy, prehash
-        [N][32]).  The device pipeline leaves c_hat where the kernels need it; hash_ag needs a host copy of it as text input."""
+        [N][32]).  The device pipeline leaves c_hat where the kernels need it; hash_ag needs a host copy of it as text input
+        (want_host=False, no hash_ag behind the call: the device pipeline downloads neither, None for both)."""
         if self.device_hash:
             try:
-                dC, pre = self.challenges_dev(vk, messages)
-                return dC, dC.numpy(), pre
+                dC, pre = self.challenges_dev(vk, messages, want_prehash=want_host)
+                return dC, (dC.numpy() if want_host else None), pre
             except FusionHipError as e:
                 if e.code != FZ_E_UNSUPPORTED:
                     raise
@@ -343,6 +347,31 @@ class BatchScheme:
         one serial SHAKE-256 over the sorted list, decode; -> (order, alpha coefficient rows scattered back to the CALLERS'
         order).  The aggregate and the target are sums over signers, so nothing else ever has to be permuted."""
         return screened_alpha_coefficients(self.P, L, R, pre, c_hat, None, threads or self.threads, order)
+
+    def _aggregate_valid(self, valid, L, R, pre, c_hat, order, sig=None, encoded=None):
+        """the shared tail of the screened aggregations: hash_ag over the signers with valid[i] set (zero coefficient rows for the
+        rest, so nothing is compacted), upload, forward transform in place, one aggregation launch, download: -> aggregate [l][d].
+        From the rows `sig` [N][l][d], or from encoded = (dB, dV): the "signature" records on the device and its own verdict
+        words, nonzero for the rest, which the fused pass takes as they are for its skip words: a rejected record is not read."""
+        _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads, order)
+        n = alpha.shape[0]
+        dAl, dO = DeviceArray.from_numpy(self.ctx, alpha), DeviceArray(self.ctx, (self.l, self.d))
+        bufs = [dAl, dO]
+        try:
+            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
+            if encoded is None:
+                dS, own = self._dev(sig, (n, self.l, self.d))
+                bufs += [dS] if own else []
+                self.ctx.aggregate_core_dev(dS.ptr, dAl.ptr, dO.ptr, n, self.l)
+            else:
+                dP = DeviceArray(self.ctx, (self.l, self.d), np.int64)
+                bufs.append(dP)
+                bound = _encoding(self.params, "signature")[2]
+                self.ctx.aggregate_encoded_async_dev(encoded[0].ptr, dAl.ptr, encoded[1].ptr, n, self.l, bound, dP.ptr, dO.ptr)
+            return dO.numpy()
+        finally:
+            for b in bufs:
+                b.free()
 
     def hash_ag_dev(self, vk, messages):
         """Everything aggregate() and verify() derive from the keys and messages, device-resident and in the callers' order:
@@ -390,7 +419,7 @@ class BatchScheme:
 
     def verify(self, vk, messages, aggregate):
         """-> (bool, reason) with the reference's reason strings (fusion.py:680-728)"""
-        n = (vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0])
+        n = self._signer_count(vk)
         if n > self.params.capacity:
             return False, VERDICT_REASONS[1]
         if n != len(messages):
@@ -410,10 +439,10 @@ class BatchScheme:
 
     # ---- one signature at a time (not in the reference) ----------------------------------------------------
     def _screen(self, vk, messages, sig, beta, omega, want_hash_ag):
-        """the per-signature verdicts of N signers, -> (codes [N] int32, dC, c_hat host copy, prehash), the last two None unless
+        """the per-signature verdicts of N signers, -> (codes [N] int32, c_hat host copy, prehash), the last two None unless
         want_hash_ag.  One challenge pass, one launch, one verdict download; vk is uploaded once (the challenge pipeline reads
         the same copy)."""
-        n = vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+        n = self._signer_count(vk)
         if n != len(messages):
             raise FusionHipError(FZ_E_BADARG, f"{n} keys but {len(messages)} messages")
         beta = signature_bound(self.params) if beta is None else int(beta)
@@ -424,38 +453,20 @@ class BatchScheme:
             if isinstance(a, DeviceArray) and (a.shape != shape or a.dtype != np.int32):
                 raise FusionHipError(FZ_E_BADARG, f"device array {a.shape} {a.dtype}: {shape} int32 expected")
         if n == 0:
-            return np.zeros(0, dtype=np.int32), None, None, None
-        dK, own_k = self._dev(vk, (n, 2, self.d))
-        dC = dS = dV = None
-        own_s = False
+            return np.zeros(0, dtype=np.int32), None, None
+        dK, own = self._dev(vk, (n, 2, self.d))
+        bufs = [dK] if own else []
         try:
-            if self.device_hash:
-                try:
-                    dC, pre = self.challenges_dev(dK, messages, want_prehash=want_hash_ag)
-                    c_hat = dC.numpy() if want_hash_ag else None
-                except FusionHipError as e:
-                    if e.code != FZ_E_UNSUPPORTED:
-                        raise
-                    self.device_hash = False
-            if dC is None:                                   # the host pipeline: parameter sets the device one does not cover
-                c_hat, pre = self.challenges(dK, messages)
-                dC = DeviceArray.from_numpy(self.ctx, c_hat)
-            dS, own_s = self._dev(sig, (n, self.l, self.d))
+            dC, c_hat, pre = self._challenges_both(dK, messages, want_hash_ag)
+            bufs.append(dC)
+            dS, own = self._dev(sig, (n, self.l, self.d))
             dV = DeviceArray(self.ctx, (n,))
+            bufs += [dS, dV] if own else [dV]
             self.ctx.verify_signatures_async_dev(self._A_dev().ptr, dS.ptr, dK.ptr, dC.ptr, n, self.l, beta, omega, dV.ptr)
-            codes = dV.numpy()
-        except Exception:
-            if dC is not None:
-                dC.free()
-            raise
+            return (dV.numpy(), c_hat, pre) if want_hash_ag else (dV.numpy(), None, None)
         finally:
-            for b, own in ((dK, own_k), (dS, own_s), (dV, True)):
-                if b is not None and own:
-                    b.free()
-        if not want_hash_ag:
-            dC.free()
-            return codes, None, None, None
-        return codes, dC, c_hat, pre
+            for b in bufs:
+                b.free()
 
     def verify_signatures(self, vk, messages, sig, beta=None, omega=None):
         """Per-signature verification (not a reference function): -> int32 codes [N], 0 where signer i's signature is valid
@@ -473,28 +484,12 @@ class BatchScheme:
         aggregate(vk[ok], messages[ok], sig[ok]) -- one bad contribution no longer spoils the aggregate, and the codes say
         whose it was.  One challenge pass serves both steps; hash_ag runs over the valid signers only, its coefficients are
         scattered back with zero rows for the rejected ones, so the signature rows are never compacted."""
-        codes, dC, c_hat, pre = self._screen(vk, messages, sig, None, None, True)
-        if dC is None:
+        codes, c_hat, pre = self._screen(vk, messages, sig, None, None, True)
+        valid = codes == 0
+        if not valid.any():
             return None, codes
-        dAl = dO = dS = None
-        own = False
-        try:
-            valid = codes == 0
-            if not valid.any():
-                return None, codes
-            _, L, R = self._split_vk(vk)
-            _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads)
-            n = alpha.shape[0]
-            dAl = DeviceArray.from_numpy(self.ctx, alpha)
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
-            dS, own = self._dev(sig, (n, self.l, self.d))
-            dO = DeviceArray(self.ctx, (self.l, self.d))
-            self.ctx.aggregate_core_dev(dS.ptr, dAl.ptr, dO.ptr, n, self.l)
-            return dO.numpy(), codes
-        finally:
-            for b, o in ((dC, True), (dAl, True), (dO, True), (dS, own)):
-                if b is not None and o:
-                    b.free()
+        _, L, R = self._split_vk(vk)
+        return self._aggregate_valid(valid, L, R, pre, c_hat, None, sig=sig), codes
 
     # ---- compact byte encoding (not in the reference; INTEGRATION.md section G) ------------------------------------
     def encode(self, kind, rows):
@@ -516,13 +511,13 @@ class BatchScheme:
             return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
         dR, own = self._dev(rows, (n, nrows, self.d))
         dB, dV = DeviceArray(self.ctx, (n, rb), np.uint8), DeviceArray(self.ctx, (n,))
+        bufs = [dR, dB, dV] if own else [dB, dV]
         try:
             self.ctx.encode_records_async_dev(dR.ptr, n, nrows, coef, bound, dB.ptr, dV.ptr)
             return dB.numpy(), dV.numpy()
         finally:
-            for b, o in ((dR, own), (dB, True), (dV, True)):
-                if o:
-                    b.free()
+            for b in bufs:
+                b.free()
 
     def decode(self, kind, data, device=False):
         """-> (rows, codes int32 [N]): the records of `data` (bytes, bytearray, memoryview, a uint8 numpy array or a uint8
@@ -535,20 +530,19 @@ class BatchScheme:
         if n == 0:
             empty = np.zeros((0, nrows, self.d), dtype=np.int32)
             return (DeviceArray.from_numpy(self.ctx, empty) if device else empty), np.zeros(0, dtype=np.int32)
-        own = not isinstance(data, DeviceArray)
-        dB = DeviceArray.from_numpy(self.ctx, data.reshape(n, rb)) if own else data
+        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
         dR, dV = DeviceArray(self.ctx, (n, nrows, self.d)), DeviceArray(self.ctx, (n,))
+        bufs = [dR, dV] if dB is data else [dB, dR, dV]
         try:
             self.ctx.decode_records_async_dev(dB.ptr, n, nrows, coef, bound, dR.ptr, dV.ptr)
             codes = dV.numpy()
             if device:
-                out, dR = dR, None
-                return out, codes
+                bufs.remove(dR)                              # the caller's from here
+                return dR, codes
             return dR.numpy(), codes
         finally:
-            for b, o in ((dB, own), (dR, True), (dV, True)):
-                if o and b is not None:
-                    b.free()
+            for b in bufs:
+                b.free()
 
     def aggregate_encoded(self, vk, messages, data):
         """aggregate() straight from the signatures' compact bytes (`data`: N "signature" records in every form decode
@@ -565,16 +559,15 @@ class BatchScheme:
         before the device is touched."""
         nrows, _, bound, _, rb = _encoding(self.params, "signature")
         data, n = _records_input("signature", data, rb)
-        nk = vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+        nk = self._signer_count(vk)
         if not (nk == len(messages) == n):
             raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
         if n == 0:
             return None, np.zeros(0, dtype=np.int32)
-        own = not isinstance(data, DeviceArray)
-        dB = DeviceArray.from_numpy(self.ctx, data.reshape(n, rb)) if own else data
-        dV = dAl = dP = dO = None
+        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
+        dV = DeviceArray(self.ctx, (n,))
+        bufs = [dV] if dB is data else [dB, dV]
         try:
-            dV = DeviceArray(self.ctx, (n,))
             self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
             vk, L, R = self._split_vk(vk)
             order_f = self._sort_async(L, R)                # beside the check and the challenge pipeline
@@ -587,16 +580,10 @@ class BatchScheme:
             valid = codes == 0
             if not valid.any():
                 return None, codes
-            _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads, order)
-            dAl = DeviceArray.from_numpy(self.ctx, alpha)
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
-            dP, dO = DeviceArray(self.ctx, (self.l, self.d), np.int64), DeviceArray(self.ctx, (self.l, self.d))
-            self.ctx.aggregate_encoded_async_dev(dB.ptr, dAl.ptr, dV.ptr, n, self.l, bound, dP.ptr, dO.ptr)
-            return dO.numpy(), codes
+            return self._aggregate_valid(valid, L, R, pre, c_hat, order, encoded=(dB, dV)), codes
         finally:
-            for b, o in ((dB, own), (dV, True), (dAl, True), (dP, True), (dO, True)):
-                if o and b is not None:
-                    b.free()
+            for b in bufs:
+                b.free()
 
     # ---- verification straight from the bytes (not in the reference) ---------------------
     def _screen_encoded(self, vk, messages, data, aggregate):
@@ -604,49 +591,31 @@ class BatchScheme:
         codes).  The argument checks come before anything touches the device."""
         nrows, _, bound, _, rb = _encoding(self.params, "signature")
         data, n = _records_input("signature", data, rb)
-        nk = vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
+        nk = self._signer_count(vk)
         if not (nk == len(messages) == n):
             raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
         if isinstance(vk, DeviceArray) and (vk.shape != (n, 2, self.d) or vk.dtype != np.int32):
             raise FusionHipError(FZ_E_BADARG, f"device array {vk.shape} {vk.dtype}: {(n, 2, self.d)} int32 expected")
         if n == 0:
             return None, np.zeros(0, dtype=np.int32)
-        own_b = not isinstance(data, DeviceArray)
-        dB = dK = dC = dV = dAl = dP = dO = None
-        own_k = False
+        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
+        bufs = [] if dB is data else [dB]
         try:
-            dB = DeviceArray.from_numpy(self.ctx, data.reshape(n, rb)) if own_b else data
-            dK, own_k = self._dev(vk, (n, 2, self.d))
-            c_hat = pre = None
-            if self.device_hash:
-                try:
-                    dC, pre = self.challenges_dev(dK, messages, want_prehash=aggregate)
-                    c_hat = dC.numpy() if aggregate else None
-                except FusionHipError as e:
-                    if e.code != FZ_E_UNSUPPORTED:
-                        raise
-                    self.device_hash = False
-            if dC is None:                                   # the host pipeline: parameter sets the device one does not cover
-                c_hat, pre = self.challenges(dK, messages)
-                dC = DeviceArray.from_numpy(self.ctx, c_hat)
+            dK, own = self._dev(vk, (n, 2, self.d))
             dV = DeviceArray(self.ctx, (n,))
+            bufs += [dK, dV] if own else [dV]
+            dC, c_hat, pre = self._challenges_both(dK, messages, aggregate)
+            bufs.append(dC)
             self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
             codes = dV.numpy()
             valid = codes == 0
             if not aggregate or not valid.any():
                 return None, codes
             _, L, R = self._split_vk(vk)
-            _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads)
-            dAl = DeviceArray.from_numpy(self.ctx, alpha)
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
-            dP, dO = DeviceArray(self.ctx, (self.l, self.d), np.int64), DeviceArray(self.ctx, (self.l, self.d))
-            # the verdict words as they are: a record with any code but 0 is skipped, its bytes not read again
-            self.ctx.aggregate_encoded_async_dev(dB.ptr, dAl.ptr, dV.ptr, n, self.l, bound, dP.ptr, dO.ptr)
-            return dO.numpy(), codes
+            return self._aggregate_valid(valid, L, R, pre, c_hat, None, encoded=(dB, dV)), codes
         finally:
-            for b, o in ((dB, own_b), (dK, own_k), (dC, True), (dV, True), (dAl, True), (dP, True), (dO, True)):
-                if o and b is not None:
-                    b.free()
+            for b in bufs:
+                b.free()
 
     def verify_signatures_encoded(self, vk, messages, data):
         """verify_signatures straight from the signatures' compact bytes (`data`: N "signature" records in every form decode
@@ -676,20 +645,18 @@ class BatchScheme:
         data, nrec = _records_input("aggregate", data, rb)
         if nrec != 1:
             raise FusionHipError(FZ_E_BADARG, f"{nrec} 'aggregate' records: exactly one expected")
-        n = (vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0])
+        n = self._signer_count(vk)
         if n > self.params.capacity:
             return False, VERDICT_REASONS[1]
         if n != len(messages):
             return False, VERDICT_REASONS[2]
-        own = not isinstance(data, DeviceArray)
         dC, dAl, _, L, R = self.hash_ag_dev(vk, messages)
         bufs = [dC, dAl]
         try:
             dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
             bufs += [dL, dR]
-            dB = DeviceArray.from_numpy(self.ctx, data.reshape(1, rb)) if own else data
-            if own:
-                bufs.append(dB)
+            dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(1, rb))
+            bufs += [] if dB is data else [dB]
             dT64, dT, dV = DeviceArray(self.ctx, (self.d,), np.int64), DeviceArray(self.ctx, (self.d,)), DeviceArray(self.ctx, (1,))
             bufs += [dT64, dT, dV]
             self.ctx.target_partial_dev(dL.ptr, dR.ptr, dC.ptr, dAl.ptr, dT64.ptr, n)
