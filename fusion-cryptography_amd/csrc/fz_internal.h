@@ -321,7 +321,7 @@ void fz_host_vk_text_parts(const fz_scheme_params *P, char *s0, int *n0, char *s
 size_t fz_host_challenge_needed_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes);
 bool fz_host_params_ok(const fz_scheme_params *P);
 
-// launchers (fz_pointwise.hip)
+// launchers of the streaming kernels (fz_pointwise.hip; fz_launch_aggregate: fz_aggregate.hip)
 int fz_launch_fill_synthetic(fz_ctx *ctx, int32_t *out, size_t count, unsigned long long seed);
 int fz_launch_bcast_rows(fz_ctx *ctx, const int32_t *in, int32_t *out, size_t segments, int l);
 enum { FZ_OP_MUL = 0, FZ_OP_ADD = 1, FZ_OP_SUB = 2, FZ_OP_NEG = 3, FZ_OP_MULACC = 4 };

@@ -2,7 +2,7 @@
 //
 // The reference transforms any power-of-two length over any odd modulus with whatever twiddle table it is handed
 // (algebra/ntt.py:239-290, :345-377; Python integers, no size limit), and its polynomial classes add, negate and multiply
-// over any modulus (algebra/polynomials.py:140-216, :272-333).  The int32 path (fz_ntt.hip, fz_pointwise.hip) covers q < 2^32 and
+// over any modulus (algebra/polynomials.py:140-216, :272-333).  The int32 path (fz_ntt.hip, fz_pointwise.hip, fz_aggregate.hip) covers q < 2^32 and
 // lengths up to 4096 -- every parameter set the scheme defines -- at full speed; this file is what stands behind the drop-in
 // packages for everything else, so that no parameter the reference accepts below 2^63 is refused and none is computed on the
 // CPU.  It is written for correctness, not bandwidth: int64 rows of centred residues in and out, canonical residues in

@@ -15,6 +15,8 @@ from isa_diff import family, metadata  # noqa: E402,F401  (the metadata parser a
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fusion-cryptography_amd", "csrc")
 # the units the transform kernels and what is built on them are compiled in: 232 kernels (test_isa_checks.py pins them per family)
 TRANSFORM_UNITS = ("fz_transforms", "fz_records")
+# the units of the streaming kernels: 37 kernels (test_isa_checks.py pins them per family, aggregation's in its own unit)
+STREAM_UNITS = ("fz_pointwise", "fz_aggregate")
 
 
 @functools.lru_cache(maxsize=None)

@@ -125,7 +125,7 @@ def sign_agg_expected(n, l, d, q):
     return np.broadcast_to(np.array(row, dtype=np.int64), (l, d)).copy()
 
 
-# ---- the aggregation kernels' per-lane sums (fz_launch_aggregate, fz_pointwise.hip) --------------------------------------
+# ---- the aggregation kernels' per-lane sums (fz_launch_aggregate, fz_aggregate.hip) --------------------------------------
 AGG_WAVES, AGG_DEPTH, AGG_R, AGG_FOLD = 8, 3, 4, 16
 
 

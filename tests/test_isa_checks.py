@@ -12,7 +12,7 @@ breaks it fails the CPU suite instead of producing a rare wrong verdict:
 import collections
 import re
 
-from _isa import TRANSFORM_UNITS, asm, bodies, family, metadata
+from _isa import STREAM_UNITS, TRANSFORM_UNITS, asm, bodies, family, metadata
 
 # kernels per family: the host dispatch instantiates one for every (degree, multiply form, shape) it can launch and no other
 KERNELS = {"ntt_fwd16": 8, "ntt_inv16": 8, "ntt_fwd4": 20, "ntt_inv4": 20, "ntt_jobs4": 60, "ntt_jobs16": 12, "ntt_jobs16_keep": 24,
@@ -28,6 +28,21 @@ def test_the_units_hold_the_kernels_of_every_family_and_no_other():
             got["diag_*" if f.startswith("diag_") else f] += 1
     assert dict(got) == KERNELS
     assert sum(got.values()) == 232
+
+
+# the two units of streaming kernels: what the launchers of fz_pointwise.hip and fz_aggregate.hip can launch and no other
+STREAM_KERNELS = {"pw_kernel": 5, "matvec_sliced_kernel": 5, "aggregate_onepass": 9, "aggregate_direct": 4, "pw_bcast_kernel": 1,
+                  "matvec_kernel": 1, "matvec_split_kernel": 1, "matvec_scalar_kernel": 1, "sign_kernel": 1, "sign_scalar_kernel": 1,
+                  "aggregate_generic_kernel": 1, "target_kernel": 1, "zero_i64_kernel": 1, "reduce_i64_kernel": 1,
+                  "norm_weight_kernel": 1, "verdict_kernel": 1, "bcast_rows_kernel": 1, "fill_synthetic_kernel": 1}
+
+
+def test_the_streaming_units_hold_the_kernels_of_every_family_and_aggregation_has_its_own():
+    got = {unit: collections.Counter(family(name) for name in metadata(asm(unit))) for unit in STREAM_UNITS}
+    assert dict(got["fz_pointwise"] + got["fz_aggregate"]) == STREAM_KERNELS
+    assert sum(STREAM_KERNELS.values()) == 37
+    assert set(got["fz_aggregate"]) == {f for f in STREAM_KERNELS if f.startswith("aggregate_")}
+    assert not set(got["fz_pointwise"]) & set(got["fz_aggregate"])
 
 
 def test_verify_fused_orders_its_adds_before_the_arrival():
@@ -54,7 +69,7 @@ def test_aggregate_onepass_instantiations_do_not_spill_and_add_with_returning_at
     ragged / fused signing) keep their state in registers -- no scratch (a spill in the signer loop would double the launch) --
     and every cross-workgroup sum is added with a RETURNING 64-bit atomic (the arrival count travels in the word the add returns),
     paired with the one non-returning add that re-arms the word"""
-    text = asm("fz_pointwise")
+    text = asm("fz_aggregate")
     meta = metadata(text, "aggregate_onepass")
     assert len(meta) == 9, sorted(meta)
     for name, f in meta.items():
