@@ -387,7 +387,7 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
 }
 
-// compact byte encoding: the checks of all five entries, in the order that decides the return code when more than one thing is
+// compact byte encoding: the checks of all six entries, in the order that decides the return code when more than one thing is
 // wrong: context, rows and bound; n == 0 is FZ_OK from here on; the entry's pointers (`ptrs_wrong`: what is wrong with them, NULL
 // when nothing is -- which pointers an entry takes and how they must be aligned is its own business); degree; size.
 // -> *w = bit_length(2 * bound).  Conditions of an entry that hold whatever n is come before this call, its own limits after it.
@@ -434,6 +434,19 @@ int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int r
     if (n == 0) return FZ_OK;
     FZ_DEV(ctx);
     return fz_launch_records(ctx, true, d_bytes, d_rows, n, rows, coef != 0, w, bound, d_status);
+}
+
+// sigma = left_sk_hat * c_hat + right_sk_hat (fusion/fusion.py:534-557) and its encoding in one pass: the signature's rows never
+// reach memory
+int fz_sign_encoded_async(fz_ctx *ctx, const int32_t *d_sk_hat, const int32_t *d_c_hat, size_t N, int l, int64_t bound, uint8_t *d_bytes,
+                          int *d_status) {
+    int w = 0;
+    const char *ptrs_wrong = records_ptrs(d_sk_hat, d_bytes, d_status);
+    if (!ptrs_wrong) ptrs_wrong = records_ptrs(d_c_hat, d_c_hat, d_c_hat);
+    FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
+    if (N == 0) return FZ_OK;
+    FZ_DEV(ctx);
+    return fz_launch_sign_encoded(ctx, d_sk_hat, d_c_hat, N, l, w, bound, d_bytes, d_status);
 }
 
 int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status) {

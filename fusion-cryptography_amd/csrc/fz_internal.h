@@ -82,6 +82,7 @@ struct fz_ctx {
     int grid_pm16;               // ... of its 16-per-lane form
     int grid_rec[4];             // ... of the byte-encoding kernels: [encode, decode] x [coefficient kinds, keys] (degree 64 / 256)
     int grid_aggenc, grid_check; // ... of aggregate_encoded and encoded_check (fz_aggregate_encoded.hip; degree 64 / 256)
+    int grid_signenc;            // ... of sign_encode (fz_sign_encoded.hip; degree 64 / 256)
     // verification from the bytes with several workgroups per record (fz_verify_encoded.hip; degree 64 / 256): a slot of int64 sums
     // and a status word per record, venc_bytes in all; allocated once at context creation (fz_verify_encoded_setup), never grown --
     // the entry is allocation-free and capturable from its first call -- and released by fz_ctx_destroy
@@ -274,6 +275,16 @@ static inline size_t fz_record_bytes(int degree, int rows, int w) { return (size
 int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
                       int *d_status);
 int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_rec (fz_ntt_query_grid calls it)
+// the follow-up of every launch that leaves records and status words: record i of `dst` (rec_bytes each, a multiple of 8) is
+// zeroed where d_status[i] != 0
+int fz_launch_records_zero(fz_ctx *ctx, const int *d_status, size_t n, void *dst, size_t rec_bytes);
+
+// signing straight to the bytes (fz_sign_encoded.hip; degree 64 / 256): record i of d_bytes = the encoding of
+// cent(cent(L_i (.) c_i) + R_i) from sk_hat [n][2][l][degree] and c_hat [n][degree], any int32; d_status [n] cleared, then 0 or
+// FZ_VERDICT_NORM; refused records zeroed
+int fz_sign_encoded_query_grid(fz_ctx *ctx);                       // ctx->grid_signenc (context creation: fz_verify_encoded_setup calls it)
+int fz_launch_sign_encoded(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat, size_t n, int l, int w, int64_t bound,
+                           uint8_t *d_bytes, int *d_status);
 
 // the byte encoding's consumers without rows (fz_aggregate_encoded.hip; degree 64 / 256): the range check of a byte stream alone
 // (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from
@@ -287,7 +298,7 @@ int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t
 // verification straight from the bytes (fz_verify_encoded.hip; degree 64 / 256): d_verdict [N] = 0, FZ_VERDICT_TARGET_MISMATCH or
 // FZ_VERDICT_ENCODING of N records of l rows against `target` [N][degree] (any residues) or, when vk != NULL, against
 // cent(vkL (.) c + vkR) from vk [N][2][degree] and chal [N][degree].  Records are multiples of 16 bytes.
-int fz_verify_encoded_setup(fz_ctx *ctx);                          // ctx->d_venc (context creation: fz_aggregate_encoded_query_grid calls it)
+int fz_verify_encoded_setup(fz_ctx *ctx);                          // ctx->d_venc, then fz_sign_encoded_query_grid (context creation: fz_aggregate_encoded_query_grid calls it)
 int fz_launch_verify_encoded(fz_ctx *ctx, const int32_t *A, const uint8_t *bytes, size_t N, int l, int w, int64_t bound,
                              const int32_t *target, const int32_t *vk, const int32_t *chal, int *d_verdict);
 

@@ -4,45 +4,8 @@
 #include "../../include/fusion_hip.h"
 
 namespace {
-// the format of the records, the packed chunk, the field unpacking, the status flag and the record walk: fz_records_dev.h
-
-// the chunk's units to the stream (streaming stores; an 8-byte last unit as such, nothing past the end)
-__device__ __forceinline__ void packed_store(uint8_t *out, size_t task, size_t total_bytes, int w, int lane, const Packed &c) {
-    const size_t base = task * 128 * (size_t)w;
-    const size_t left = total_bytes - base;
-    const unsigned cb = (unsigned)(left < (size_t)128 * w ? left : (size_t)128 * w);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (64u * 16u * j < cb) {
-            const unsigned off = 16u * (64u * j + lane);
-            if (off + 16 <= cb) {
-                fz_v4i t = {c.u[j].x, c.u[j].y, c.u[j].z, c.u[j].w};
-                __builtin_nontemporal_store(t, reinterpret_cast<fz_v4i *>(out + base + off));
-            } else if (off < cb) {
-                fz_v2i t = {c.u[j].x, c.u[j].y};
-                __builtin_nontemporal_store(t, reinterpret_cast<fz_v2i *>(out + base + off));
-            }
-        }
-    }
-}
-
-// a lane's 16 fields (u < 2^w) -> its w 16-bit words at dst.  The bit count `nb` depends on w only: the emits are uniform branches.
-__device__ __forceinline__ void fields_pack(uint16_t *dst, const uint32_t (&u)[16], int w) {
-    unsigned long long acc = 0;
-    int nb = 0, o = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        acc |= (unsigned long long)u[k] << nb;      // nb < 16: at most 47 bits held
-        nb += w;
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-            if (nb >= 16) {
-                dst[o++] = (uint16_t)acc;
-                acc >>= 16;
-                nb -= 16;
-            }
-    }
-}
+// the format of the records, the packed chunk and its loads and stores, the field packing and unpacking, the status flag and the
+// record walk: fz_records_dev.h
 
 // encode: rows [records][rec_values] int32 -> the byte stream; status word of a record |= FZ_VERDICT_NORM where some |z| > B
 template <int LOGD, bool FAST, bool COEF>
@@ -258,9 +221,12 @@ int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size
         });
     if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "records launch");
     if (rc != FZ_OK) return rc;
-    const size_t rec_bytes = decode ? (size_t)rv * sizeof(int32_t) : fz_record_bytes(ctx->degree, rows, w);
+    return fz_launch_records_zero(ctx, d_status, n, dst, decode ? (size_t)rv * sizeof(int32_t) : fz_record_bytes(ctx->degree, rows, w));
+}
+
+int fz_launch_records_zero(fz_ctx *ctx, const int *d_status, size_t n, void *dst, size_t rec_bytes) {
     const size_t zcap = (size_t)ctx->num_cu * 4;
-    hipLaunchKernelGGL(records_zero_failed, dim3((unsigned)(n < zcap ? n : zcap)), dim3(256), 0, ctx->stream, (const int *)d_status, n,
-                       (uint8_t *)dst, rec_bytes);
+    hipLaunchKernelGGL(records_zero_failed, dim3((unsigned)(n < zcap ? n : zcap)), dim3(256), 0, ctx->stream, d_status, n, (uint8_t *)dst,
+                       rec_bytes);
     return fz_check_hip(hipGetLastError(), "records zeroing launch");
 }

@@ -1,8 +1,9 @@
 // fz_records_dev.h -- the device building blocks of the compact byte encoding that more than one unit uses (fz_records.hip: the
 // records_* kernels; fz_aggregate_encoded.hip: the range check and the aggregation straight from the bytes; fz_verify_encoded.hip:
-// the verification straight from the bytes): the packed chunk of the chunk walk, the field unpacking, the steps from the packed
-// chunk to the transform's outputs and their sums, the per-record status flag and the record walk.  No kernels and no host code
-// here; everything is private to the unit that includes it.
+// the verification straight from the bytes; fz_sign_encoded.hip: signing straight to the bytes): the packed chunk of the chunk
+// walk with its loads and stores, the field packing and unpacking, the steps from the packed chunk to the transform's outputs and
+// their sums, the per-record status flag and the record walk.  No kernels and no host code here; everything is private to the
+// unit that includes it.
 #ifndef FZ_RECORDS_DEV_H
 #define FZ_RECORDS_DEV_H
 
@@ -57,6 +58,26 @@ __device__ __forceinline__ Packed packed_load(const uint8_t *in, size_t task, si
     return c;
 }
 
+// the chunk's units to the stream (streaming stores; an 8-byte last unit as such, nothing past the end)
+__device__ __forceinline__ void packed_store(uint8_t *out, size_t task, size_t total_bytes, int w, int lane, const Packed &c) {
+    const size_t base = task * 128 * (size_t)w;
+    const size_t left = total_bytes - base;
+    const unsigned cb = (unsigned)(left < (size_t)128 * w ? left : (size_t)128 * w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (64u * 16u * j < cb) {
+            const unsigned off = 16u * (64u * j + lane);
+            if (off + 16 <= cb) {
+                fz_v4i t = {c.u[j].x, c.u[j].y, c.u[j].z, c.u[j].w};
+                __builtin_nontemporal_store(t, reinterpret_cast<fz_v4i *>(out + base + off));
+            } else if (off < cb) {
+                fz_v2i t = {c.u[j].x, c.u[j].y};
+                __builtin_nontemporal_store(t, reinterpret_cast<fz_v2i *>(out + base + off));
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ void packed_to_lds(uint8_t *pk, const Packed &c, int w, int lane) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -71,6 +92,24 @@ __device__ __forceinline__ Packed packed_from_lds(const uint8_t *pk, int w, int 
         if (64 * j < 8 * w && 64 * j + lane < 8 * w) c.u[j] = *reinterpret_cast<const int4 *>(pk + 16 * (64 * j + lane));
     }
     return c;
+}
+
+// a lane's 16 fields (u < 2^w) -> its w 16-bit words at dst.  The bit count `nb` depends on w only: the emits are uniform branches.
+__device__ __forceinline__ void fields_pack(uint16_t *dst, const uint32_t (&u)[16], int w) {
+    unsigned long long acc = 0;
+    int nb = 0, o = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        acc |= (unsigned long long)u[k] << nb;      // nb < 16: at most 47 bits held
+        nb += w;
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            if (nb >= 16) {
+                dst[o++] = (uint16_t)acc;
+                acc >>= 16;
+                nb -= 16;
+            }
+    }
 }
 
 // ... and back: the lane's w words at src -> its 16 fields (exactly w words are read)

@@ -572,6 +572,23 @@ def to_bytes(params: Params, obj, aggregate: bool = False) -> bytes:
     return data.tobytes()
 
 
+def sign_to_bytes(params: Params, key: OneTimeKeyTuple, message: str) -> bytes:
+    """NOT in the reference: to_bytes(params, sign(params, key, message)) without the Signature in between -- the challenge as
+    sign() takes it (hash_ch, whoever stands behind that name), then one fz_sign_encoded_async call that signs and packs.  Raises
+    ValueError with the reason when the signature is over the bound of one signature, as to_bytes does."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import signature_bound
+    sk, vk = key
+    bound = signature_bound(params)
+    c_hat = hash_ch(params=params, key=vk, message=message).c_hat
+    q = params.modulus
+    sk_hat = np.stack([_rows_of(sk.left_sk_hat, q), _rows_of(sk.right_sk_hat, q)])[None]
+    data, codes = _ctx(params).sign_encoded(sk_hat, c_hat._i32()[None], bound)
+    if codes[0]:
+        raise ValueError(ENCODING_REASONS[int(codes[0])])
+    return data.tobytes()
+
+
 def from_bytes(params: Params, kind: str, data: bytes):
     """NOT in the reference: the inverse of to_bytes for one record of `kind` ("vk", "signature" or "aggregate") -> a
     OneTimeVerificationKey or a Signature.  Raises ValueError for a wrong length or a record that is not canonical."""

@@ -405,6 +405,13 @@ class Context:
         check(self._lib, self._lib.fz_encode_records_async(self._h, c_void_p(d_rows), n, rows, 1 if coef else 0, bound,
                                                            c_void_p(d_bytes), c_void_p(d_status)))
 
+    def sign_encoded_async_dev(self, d_sk_hat, d_c_hat, n, l, bound, d_bytes, d_status):
+        """signing straight to the bytes: record i of d_bytes = the encoding of cent(L_i (.) c_i + R_i) from d_sk_hat [n][2][l][d]
+        and d_c_hat [n][d], exactly what sign_core_dev followed by encode_records_async_dev(rows = l, coef) leaves, without the
+        int32 rows; codes (0, 4) to d_status [n], a refused record's bytes zero (asynchronous)"""
+        check(self._lib, self._lib.fz_sign_encoded_async(self._h, c_void_p(d_sk_hat), c_void_p(d_c_hat), n, l, bound,
+                                                         c_void_p(d_bytes), c_void_p(d_status)))
+
     def decode_records_async_dev(self, d_bytes, n, rows, coef, bound, d_rows, d_status):
         """... and back: codes (0, 6) to d_status [n], a refused record's rows zero (asynchronous)"""
         check(self._lib, self._lib.fz_decode_records_async(self._h, c_void_p(d_bytes), n, rows, 1 if coef else 0, bound,
@@ -568,6 +575,25 @@ class Context:
             return dS.to_numpy(np.int32, (batch, l, d))
         finally:
             for b in (dK, dC, dS):
+                b.free()
+
+    def sign_encoded(self, sk_hat, c_hat, bound):
+        """sk_hat [batch][2][l][d]; c_hat [batch][d] -> (data uint8 [batch][l * d * w / 8], codes int32 [batch]): the compact
+        bytes of sign_core's signatures under `bound` in one pass (sign_encoded_async_dev), codes 0 or 4."""
+        sk, c = _as_i32(sk_hat), _as_i32(c_hat)
+        batch, _, l, d = sk.shape
+        rb = l * d * (2 * int(bound)).bit_length() // 8
+        bufs = []
+        try:
+            for a in (sk, c.reshape(batch, d)):
+                bufs.append(DeviceBuffer.from_numpy(self, a))
+            for nbytes in (batch * rb, batch * 4):
+                bufs.append(DeviceBuffer(self, max(1, nbytes)))
+            dK, dC, dB, dV = bufs
+            self.sign_encoded_async_dev(dK.ptr, dC.ptr, batch, l, int(bound), dB.ptr, dV.ptr)
+            return dB.to_numpy(np.uint8, (batch, rb)), dV.to_numpy(np.int32, (batch,))
+        finally:
+            for b in bufs:
                 b.free()
 
     def aggregate_core(self, sig, alpha_hat):

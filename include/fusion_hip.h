@@ -335,6 +335,17 @@ FZ_API int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n,
 FZ_API int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int coef, int64_t bound,
                                    int32_t *d_rows, int *d_status);
 
+/* signing straight to the bytes (fusion/fusion.py:534-557 and the encoding of its result in one pass; no int32 row of the
+ * signature reaches memory): record i of d_bytes [N][l * degree * w / 8] is exactly what fz_sign_core followed by
+ * fz_encode_records_async(rows = l, coef = 1, bound) leaves, d_status[i] = 0 or FZ_VERDICT_NORM (some |z| > bound; the record's
+ * bytes are zero).  d_sk_hat [N][2][l][degree] and d_c_hat [N][degree] take any int32 value and are not written.  Rules of
+ * fz_encode_records_async: degree 64 or 256 (else FZ_E_UNSUPPORTED), 1 <= bound <= (q-1)/2, l >= 1, all four pointers 16-byte
+ * aligned, N == 0 does nothing and writes nothing; a stream whose last 16-byte unit is half full (degree 64, l * w and N odd)
+ * ends there.  Asynchronous on the context's stream, allocation-free, capturable by fz_graph_* (the clear of d_status and the
+ * zeroing of refused records are part of the captured work). */
+FZ_API int fz_sign_encoded_async(fz_ctx *ctx, const int32_t *d_sk_hat, const int32_t *d_c_hat, size_t N, int l, int64_t bound,
+                                 uint8_t *d_bytes, int *d_status);
+
 /* the range check of fz_decode_records_async alone (no transform, no rows): status per record 0 or FZ_VERDICT_ENCODING (a field
  * > 2 * bound); nothing else is written.  Same arguments and rules as fz_decode_records_async, for either kind of record. */
 FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status);
