@@ -387,7 +387,7 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
 }
 
-// compact byte encoding: the checks of all six entries, in the order that decides the return code when more than one thing is
+// compact byte encoding: the checks of all seven entries, in the order that decides the return code when more than one thing is
 // wrong: context, rows and bound; n == 0 is FZ_OK from here on; the entry's pointers (`ptrs_wrong`: what is wrong with them, NULL
 // when nothing is -- which pointers an entry takes and how they must be aligned is its own business); degree; size.
 // -> *w = bit_length(2 * bound).  Conditions of an entry that hold whatever n is come before this call, its own limits after it.
@@ -469,6 +469,34 @@ int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_
         return fz_set_error(FZ_E_UNSUPPORTED, "N=%zu too large for exact fp64 accumulation (< 2^22)", N);
     FZ_DEV(ctx);
     return fz_launch_aggregate_encoded(ctx, d_bytes, d_alpha_hat, d_skip, N, l, w, bound, d_partial, d_out);
+}
+
+// many committees in one launch: group g owns records [h_offsets[g], h_offsets[g + 1]).  The argument rules are
+// fz_aggregate_encoded_async's, in its order, then the offsets and the stride.
+int fz_aggregate_encoded_ragged_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
+                                      const size_t *h_offsets, size_t groups, int l, int64_t bound, int64_t *d_partial,
+                                      size_t partial_stride, int32_t *d_out) {
+    int w = 0;
+    FZ_REQUIRE(groups == 0 || h_offsets, "NULL argument");
+    const size_t total = groups ? h_offsets[groups] : 0;
+    FZ_REQUIRE(total == 0 || d_alpha_hat, "NULL argument");
+    FZ_REQUIRE((((uintptr_t)d_alpha_hat | (uintptr_t)d_out) & 15) == 0, "alpha_hat and the aggregates must be 16-byte aligned");
+    // (a call whose groups are all empty reads no byte: the stream may be NULL then)
+    FZ_TRY(records_args(ctx, groups == 0 ? 0 : (total ? total : 1), l, bound, records_ptrs(total ? (const void *)d_bytes : (const void *)d_partial, d_partial,
+                                                           total ? (const void *)d_alpha_hat : (const void *)d_partial), &w));
+    if (groups == 0) return FZ_OK;
+    FZ_TRY(records_whole_units(ctx, l, w));
+    for (size_t g = 0; g < groups; ++g) FZ_REQUIRE(h_offsets[g] <= h_offsets[g + 1], "offsets must not decrease");
+    FZ_REQUIRE(groups == 1 || (partial_stride >= (size_t)l * ctx->degree && (partial_stride & 1) == 0),
+               "partial_stride must be at least l * degree, and even (16-byte aligned partials)");
+    for (size_t g = 0; g < groups; ++g)
+        if (h_offsets[g + 1] - h_offsets[g] >= ((size_t)1 << 22))
+            return fz_set_error(FZ_E_UNSUPPORTED, "group %zu: %zu signers are too many for exact fp64 accumulation (< 2^22)", g,
+                                h_offsets[g + 1] - h_offsets[g]);
+    if (total >= 0xffffffc0ull) return fz_set_error(FZ_E_UNSUPPORTED, "%zu records in one call: signer indices are 32-bit", total);
+    FZ_DEV(ctx);
+    return fz_launch_aggregate_encoded_ragged(ctx, d_bytes, d_alpha_hat, d_skip, h_offsets, groups, l, w, bound, d_partial, partial_stride,
+                                              d_out);
 }
 
 int fz_verify_encoded_async(fz_ctx *ctx, const int32_t *d_A, const uint8_t *d_bytes, size_t N, int l, int64_t bound,

@@ -83,6 +83,7 @@ struct fz_ctx {
     int grid_rec[4];             // ... of the byte-encoding kernels: [encode, decode] x [coefficient kinds, keys] (degree 64 / 256)
     int grid_aggenc, grid_check; // ... of aggregate_encoded and encoded_check (fz_aggregate_encoded.hip; degree 64 / 256)
     int grid_signenc;            // ... of sign_encode (fz_sign_encoded.hip; degree 64 / 256)
+    int grid_aggenc_rag;         // ... of aggregate_encoded_ragged (fz_aggregate_many_encoded.hip; degree 64 / 256)
     // verification from the bytes with several workgroups per record (fz_verify_encoded.hip; degree 64 / 256): a slot of int64 sums
     // and a status word per record, venc_bytes in all; allocated once at context creation (fz_verify_encoded_setup), never grown --
     // the entry is allocation-free and capturable from its first call -- and released by fz_ctx_destroy
@@ -282,7 +283,7 @@ int fz_launch_records_zero(fz_ctx *ctx, const int *d_status, size_t n, void *dst
 // signing straight to the bytes (fz_sign_encoded.hip; degree 64 / 256): record i of d_bytes = the encoding of
 // cent(cent(L_i (.) c_i) + R_i) from sk_hat [n][2][l][degree] and c_hat [n][degree], any int32; d_status [n] cleared, then 0 or
 // FZ_VERDICT_NORM; refused records zeroed
-int fz_sign_encoded_query_grid(fz_ctx *ctx);                       // ctx->grid_signenc (context creation: fz_verify_encoded_setup calls it)
+int fz_sign_encoded_query_grid(fz_ctx *ctx);                       // ctx->grid_signenc, then fz_aggregate_many_encoded_query_grid (context creation: fz_verify_encoded_setup calls it)
 int fz_launch_sign_encoded(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat, size_t n, int l, int w, int64_t bound,
                            uint8_t *d_bytes, int *d_status);
 
@@ -294,6 +295,14 @@ int fz_aggregate_encoded_query_grid(fz_ctx *ctx);                  // ctx->grid_
 int fz_launch_check_records(fz_ctx *ctx, const uint8_t *bytes, size_t n, int rows, int w, int64_t bound, int *d_status);
 int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, int l, int w,
                                 int64_t bound, int64_t *d_partial, int32_t *d_out);
+
+// many aggregates of different sizes straight from the bytes in one launch (fz_aggregate_many_encoded.hip; degree 64 / 256): group g
+// of `groups` owns records [h_offsets[g], h_offsets[g + 1]) of the concatenated byte stream and the same rows of alpha and skip;
+// its int64 partial [l][degree] at d_partial + g * pstride is zeroed, then summed as fz_launch_aggregate_encoded does; d_out
+// [groups][l][degree] = cent(partial) when not NULL.  h_offsets is read before the call returns.
+int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx);             // ctx->grid_aggenc_rag (context creation: fz_sign_encoded_query_grid calls it)
+int fz_launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const size_t *h_offsets,
+                                       size_t groups, int l, int w, int64_t bound, int64_t *d_partial, size_t pstride, int32_t *d_out);
 
 // verification straight from the bytes (fz_verify_encoded.hip; degree 64 / 256): d_verdict [N] = 0, FZ_VERDICT_TARGET_MISMATCH or
 // FZ_VERDICT_ENCODING of N records of l rows against `target` [N][degree] (any residues) or, when vk != NULL, against

@@ -681,6 +681,78 @@ def verify_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messag
         bs.close()
 
 
+def _groups_for_many(params: Params, keys_per_group, messages_per_group):
+    """the concatenated key rows, messages and sizes of G groups of signers; ValueError (naming the group) for unequal numbers of
+    groups, a group without signers and a group with unequal numbers of keys and messages"""
+    from fusion_hip.scheme import vk_from_object
+    if len(keys_per_group) != len(messages_per_group):
+        raise ValueError(f"{len(keys_per_group)} groups of keys, {len(messages_per_group)} groups of messages")
+    for g, (k, m) in enumerate(zip(keys_per_group, messages_per_group)):
+        if len(k) != len(m):
+            raise ValueError(f"group {g}: {len(k)} keys, {len(m)} messages")
+        if not len(k):
+            raise ValueError(f"group {g}: no signers")
+    return (lambda: np.stack([vk_from_object(params, k) for ks in keys_per_group for k in ks]),
+            [m for ms in messages_per_group for m in ms], [len(ks) for ks in keys_per_group])
+
+
+def aggregate_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],
+                              blobs_per_group: List[List[bytes]]) -> List[Signature]:
+    """NOT in the reference: aggregate_from_bytes for G committees at once -> [Signature] * G, entry g what
+    aggregate_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs_per_group[g]) returns
+    (BatchScheme.aggregate_many_encoded: one launch over all committees' bytes).  Raises ValueError, naming the group and the
+    record, for unequal numbers of groups, of keys, messages and blobs of a group, for a group without signers, for a blob of
+    the wrong length and for a record that is not canonical (the first one, with the reason)."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import BatchScheme, encoded_size
+    if len(blobs_per_group) != len(keys_per_group):
+        raise ValueError(f"{len(keys_per_group)} groups of keys, {len(blobs_per_group)} groups of records")
+    vk_rows, messages, sizes = _groups_for_many(params, keys_per_group, messages_per_group)
+    size = encoded_size(params, "signature")
+    for g, blobs in enumerate(blobs_per_group):
+        if len(blobs) != sizes[g]:
+            raise ValueError(f"group {g}: {sizes[g]} keys, {len(blobs)} records")
+        for i, b in enumerate(blobs):
+            if len(b) != size:
+                raise ValueError(f"group {g} record {i}: a 'signature' record is {size} bytes, not {len(b)}")
+    if not sizes:
+        return []
+    bs = BatchScheme(params)
+    try:
+        out, codes = bs.aggregate_many_encoded(vk_rows(), messages, b"".join(bytes(b) for blobs in blobs_per_group for b in blobs), sizes)
+    finally:
+        bs.close()
+    bad = np.flatnonzero(codes)
+    if bad.size:
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        g = int(np.searchsorted(off, bad[0], side="right")) - 1
+        raise ValueError(f"group {g} record {int(bad[0] - off[g])}: {ENCODING_REASONS[int(codes[bad[0]])]}")
+    return [Signature(signature_hat=_column(params, rows)) for rows in out]
+
+
+def verify_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],
+                           blobs: List[bytes]) -> List[Tuple[bool, str]]:
+    """NOT in the reference: verify_from_bytes for G aggregates at once (blobs[g]: the "aggregate" record of group g) ->
+    [(ok, reason)] * G, entry g what verify_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs[g]) returns
+    (BatchScheme.verify_many_encoded).  Raises ValueError, naming the group, for unequal numbers of groups, of keys and messages
+    of a group, for a group without signers and for a blob of the wrong length."""
+    from fusion_hip.scheme import BatchScheme, encoded_size
+    if len(blobs) != len(keys_per_group):
+        raise ValueError(f"{len(keys_per_group)} groups of keys, {len(blobs)} records")
+    vk_rows, messages, sizes = _groups_for_many(params, keys_per_group, messages_per_group)
+    size = encoded_size(params, "aggregate")
+    for g, b in enumerate(blobs):
+        if len(b) != size:
+            raise ValueError(f"group {g} record 0: an 'aggregate' record is {size} bytes, not {len(b)}")
+    if not sizes:
+        return []
+    bs = BatchScheme(params)
+    try:
+        return bs.verify_many_encoded(vk_rows(), messages, b"".join(bytes(b) for b in blobs), sizes)
+    finally:
+        bs.close()
+
+
 _ORIGINALS.update({name: globals()[name] for name in (
     "decode_bytes_to_polynomial_coefficients", "hash_ch", "parse_challenge", "transform", "sample_coefficient_matrix", "hash_ag",
     "sample_polynomial_coefficient_representation")})

@@ -428,6 +428,16 @@ class Context:
         check(self._lib, self._lib.fz_aggregate_encoded_async(self._h, c_void_p(d_bytes), c_void_p(d_alpha), c_void_p(d_skip or None),
                                                               N, l, bound, c_void_p(d_partial), c_void_p(d_out or None)))
 
+    def aggregate_encoded_ragged_async_dev(self, d_bytes, d_alpha, d_skip, offsets, l, bound, d_partial, partial_stride, d_out):
+        """len(offsets) - 1 aggregates of different sizes straight from the bytes in one launch: aggregate g = records
+        [offsets[g], offsets[g+1]) of the concatenated stream and the same rows of d_alpha / d_skip; its int64 partial [l][d] at
+        d_partial + g * partial_stride is what aggregate_encoded_async_dev leaves for that group alone, d_out [groups][l][d]
+        int32 = cent(partial) when not 0 / None (asynchronous; the offsets are read before the call returns)"""
+        off = (ctypes.c_size_t * len(offsets))(*[int(x) for x in offsets])
+        check(self._lib, self._lib.fz_aggregate_encoded_ragged_async(
+            self._h, c_void_p(d_bytes or None), c_void_p(d_alpha or None), c_void_p(d_skip or None), off, len(offsets) - 1, l, bound,
+            c_void_p(d_partial), partial_stride, c_void_p(d_out or None)))
+
     def verify_encoded_async_dev(self, d_A, d_bytes, N, l, bound, d_target, d_vk, d_c_hat, d_verdicts):
         """the verdicts (0, 3, 6) of N encoded records of l rows straight from their bytes, against d_target [N][d] or, with
         d_target 0 / None, against the targets formed from d_vk [N][2][d] and d_c_hat [N][d] (asynchronous)"""

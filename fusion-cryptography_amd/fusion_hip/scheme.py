@@ -801,6 +801,134 @@ class BatchScheme:
             if own:
                 dS.free()
 
+    # ---- many aggregates at once, straight from the bytes (not in the reference) ---------
+    def _many_sizes(self, vk, messages, sizes):
+        """sizes as ints, refused with FusionHipError(FZ_E_BADARG) unless each is at least 1 and they sum to the numbers of keys
+        and of messages; no device is touched"""
+        sizes = [int(x) for x in sizes]
+        if any(x < 1 for x in sizes):
+            raise FusionHipError(FZ_E_BADARG, "every aggregate needs at least one signer")
+        nk = self._signer_count(vk)
+        if not (sum(sizes) == nk == len(messages)):
+            raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {nk} keys and {len(messages)} messages were given")
+        if isinstance(vk, DeviceArray) and (vk.shape != (nk, 2, self.d) or vk.dtype != np.int32):
+            raise FusionHipError(FZ_E_BADARG, f"device array {vk.shape} {vk.dtype}: {(nk, 2, self.d)} int32 expected")
+        return sizes
+
+    def aggregate_many_encoded(self, vk, messages, data, sizes, screened=False, encoded=False):
+        """G independent aggregate_encoded calls (screened=True: aggregate_encoded_screened calls) as one batch: vk [sum N][2][d]
+        (numpy or DeviceArray), messages and `data` (sum N "signature" records in every form decode takes) hold the signers of
+        aggregate 0, then of aggregate 1, ...; sizes = signers per aggregate (they may differ, each at least 1).
+        -> (aggregates [G][l][d] int32, codes int32 [sum N]): codes[i] is 0 or 6 (ENCODING_REASONS), with screened=True 0, 3
+        (SIGNATURE_REASONS) or 6; row g is bit for bit what the single call returns for group g alone, and all zero where that
+        call returns None (no accepted signer: hash_ag does not run for the group).
+        encoded=True: bytes in, bytes out -- the aggregates are never downloaded as rows: -> (records uint8
+        [G][encoded_size(params, "aggregate")], codes, aggregate_codes int32 [G]), aggregate_codes[g] 0 or 4 as encode gives it.
+        One upload of the bytes, one range check (or one keyed verification) over all records whose status words stay on the
+        device as the skip words, one challenge pass, hash_ag per group over its accepted signers on the thread pool of
+        aggregate_many, one upload + transform of all coefficients, ONE launch for all groups (fz_aggregate_encoded_ragged_async),
+        one download.  Sizes that do not sum to the numbers of records, keys and messages, a size below 1, or a length that is
+        not whole records raise FusionHipError(FZ_E_BADARG) before the device is touched; no records and sizes == [] return
+        empty arrays without a device."""
+        from concurrent.futures import ThreadPoolExecutor
+        nrows, _, bound, _, rb = _encoding(self.params, "signature")
+        _, _, abound, _, arb = _encoding(self.params, "aggregate")
+        data, n = _records_input("signature", data, rb)
+        sizes = self._many_sizes(vk, messages, sizes)
+        if sum(sizes) != n:
+            raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {n} records were given")
+        g = len(sizes)
+        if g == 0:
+            codes = np.zeros(0, dtype=np.int32)
+            return (np.zeros((0, arb), dtype=np.uint8), codes, np.zeros(0, dtype=np.int32)) if encoded else \
+                (np.zeros((0, self.l, self.d), dtype=np.int32), codes)
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
+        bufs = [] if dB is data else [dB]
+        try:
+            dV = DeviceArray(self.ctx, (n,))
+            bufs.append(dV)
+            if screened:
+                dK, own = self._dev(vk, (n, 2, self.d))
+                bufs += [dK] if own else []
+                dC, c_hat, pre = self._challenges_both(dK, messages)
+                bufs.append(dC)
+                self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
+            else:
+                self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
+            _, L, R = self._split_vk(vk)
+            if not screened:
+                dC, c_hat, pre = self._challenges_both(vk, messages)
+                dC.free()                                   # hash_ag reads the host copy; nothing here needs c_hat on the device
+            codes = dV.numpy()
+            valid = codes == 0
+            per = max(1, self.threads // g)
+
+            def one(k):
+                a, b = off[k], off[k + 1]
+                if not valid[a:b].any():
+                    return np.zeros((b - a, self.d), dtype=np.int32)
+                return screened_alpha_coefficients(self.P, L[a:b], R[a:b], pre[a:b], c_hat[a:b], valid[a:b], per)[1]
+            with ThreadPoolExecutor(max_workers=min(g, self.threads)) as pool:      # the C calls release the GIL
+                alpha = np.concatenate(list(pool.map(one, range(g))))
+            dAl = DeviceArray.from_numpy(self.ctx, alpha)
+            bufs.append(dAl)
+            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                           # in place; a zero row stays zero
+            dP, dO = DeviceArray(self.ctx, (g, self.l, self.d), np.int64), DeviceArray(self.ctx, (g, self.l, self.d))
+            bufs += [dP, dO]
+            self.ctx.aggregate_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, off, self.l, bound, dP.ptr, self.l * self.d, dO.ptr)
+            if not encoded:
+                return dO.numpy(), codes
+            dR, dW = DeviceArray(self.ctx, (g, arb), np.uint8), DeviceArray(self.ctx, (g,))
+            bufs += [dR, dW]
+            self.ctx.encode_records_async_dev(dO.ptr, g, self.l, True, abound, dR.ptr, dW.ptr)
+            return dR.numpy(), codes, dW.numpy()
+        finally:
+            for b in bufs:
+                b.free()
+
+    def verify_many_encoded(self, vk, messages, data, sizes):
+        """G independent verify_encoded calls as one batch: `data` holds G "aggregate" records (every form decode takes), vk and
+        messages the signers of aggregate 0, then of aggregate 1, ...; sizes = signers per aggregate.  -> [(bool, reason)] * G,
+        entry g equal to verify_encoded of group g alone: a record that is not canonical gives (False, ENCODING_REASONS[6]).
+        One hash_ag pass for all groups, one launch for all verification targets, one for all verifications straight from the
+        bytes, verdicts read once; the aggregates' int32 rows never exist on the device.  Sizes that do not sum to the numbers
+        of keys and messages, a size below 1, or anything but len(sizes) whole records raise FusionHipError(FZ_E_BADARG) before
+        the device is touched."""
+        _, _, bound, _, rb = _encoding(self.params, "aggregate")
+        data, nrec = _records_input("aggregate", data, rb)
+        sizes = self._many_sizes(vk, messages, sizes)
+        g = len(sizes)
+        if nrec != g:
+            raise FusionHipError(FZ_E_BADARG, f"{nrec} 'aggregate' records but {g} sizes")
+        if g == 0:
+            return []
+        live = [i for i, n in enumerate(sizes) if n <= self.params.capacity]
+        if len(live) != g:                            # rare, as in verify_many: the capacity check first, the rest one by one
+            out = [(False, VERDICT_REASONS[1])] * g
+            vkh, _, _ = self._split_vk(vk)
+            off = np.concatenate([[0], np.cumsum(sizes)])
+            recs = (data.numpy() if isinstance(data, DeviceArray) else data).reshape(g, rb)
+            for i in live:
+                out[i] = self.verify_encoded(vkh[off[i]:off[i + 1]], messages[off[i]:off[i + 1]], recs[i])
+            return out
+        dC, dAl, off, L, R = self._hash_ag_many(vk, messages, sizes)
+        bufs = [dC, dAl]
+        try:
+            dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
+            bufs += [dL, dR]
+            dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(g, rb))
+            bufs += [] if dB is data else [dB]
+            dT64, dT, dV = DeviceArray(self.ctx, (g, self.d), np.int64), DeviceArray(self.ctx, (g, self.d)), DeviceArray(self.ctx, (g,))
+            bufs += [dT64, dT, dV]
+            self.ctx.aggregate_target_partial_ragged_dev(0, dAl.ptr, dL.ptr, dR.ptr, dC.ptr, off, self.l, 0, 0, dT64.ptr, self.d)
+            self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, g * self.d)
+            self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, g, self.l, bound, dT.ptr, 0, 0, dV.ptr)
+            return [(int(c) == 0, ENCODING_REASONS[6] if int(c) == 6 else VERDICT_REASONS[int(c)]) for c in dV.numpy()]
+        finally:
+            for b in bufs:
+                b.free()
+
 
 def _seed_array(seeds):
     """the seeds as a uint64 array when every one is a non-negative integer below 2^64 - 1 (what the C and device samplers

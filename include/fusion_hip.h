@@ -362,6 +362,23 @@ FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n,
 FZ_API int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
                                       size_t N, int l, int64_t bound, int64_t *d_partial, int32_t *d_out);
 
+/* many committees in one launch ("Many committees in one launch"): `groups` aggregates of different
+ * sizes straight from the bytes.  Group g owns records [h_offsets[g], h_offsets[g + 1]) of the concatenated byte stream d_bytes
+ * and the same rows of d_alpha_hat and d_skip; h_offsets is a HOST array of groups + 1 entries, read before the call returns.
+ * Group g's int64 partial [l][degree] lies at d_partial + g * partial_stride (partial_stride >= l * degree, and even: every
+ * partial 16-byte aligned; with groups == 1 the stride is not looked at) and holds what fz_aggregate_encoded_async leaves for
+ * that group alone; d_out [groups][l][degree] int32 = cent(partial) when not NULL.  The call clears exactly the partials it
+ * owns and overwrites them and d_out: the words between two partials are not touched.  A group of zero signers, or one whose
+ * every signer is skipped, yields a zero partial and a zero d_out row.  d_skip may be NULL; a skipped record's bytes are never
+ * read, and the fields are not range checked (as fz_aggregate_encoded_async).  Its argument rules in its order, then
+ * FZ_E_BADARG for decreasing offsets or a partial_stride that is too small, FZ_E_UNSUPPORTED for a group of 2^22 signers or more
+ * and for 2^32 - 64 records or more in all (signer indices are 32-bit); groups == 0 does nothing and writes nothing.
+ * Asynchronous on the context's stream, allocation-free, capturable by fz_graph_* (the clears are part of the captured work;
+ * the offsets are those of the capture). */
+FZ_API int fz_aggregate_encoded_ragged_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
+                                             const size_t *h_offsets, size_t groups, int l, int64_t bound, int64_t *d_partial,
+                                             size_t partial_stride, int32_t *d_out);
+
 /* verdicts of N encoded records against their targets, straight from the bytes */
 /* Record i is l rows of w-bit fields u = z + bound, z = cent(INTT(row)), exactly what fz_encode_records_async writes for a
  * signature or an aggregate.  d_verdicts[i] = FZ_VERDICT_ENCODING (6) when some field of record i is above 2 * bound (the
