@@ -273,6 +273,28 @@ def matvec_sliced_taken(knob, batch, l, d, num_cu, guard=True):
     return not split_k and (l <= 32768 or not guard) and knob >= 0
 
 
+def matvec_route(knob, batch, l, d, num_cu, aligned=True):
+    """the kernel fz_launch_matvec takes (FZ_MATVEC_SLICES = knob; aligned: A, S and out all 16-byte aligned) ->
+    "split" | ("sliced", KS) | "kernel" | "scalar"; KS as the launcher settles it: the knob's 1 | 2 | 4 | 8 | 16 (any other value:
+    by the number of waves), then halved while a slice would hold fewer than eight rows"""
+    if d % 4 or not aligned:
+        return "scalar"
+    pow2 = d & (d - 1) == 0
+    if 16 <= d <= 4096 and pow2 and (batch * (d // 4) < num_cu * 256 if knob < 0 else (knob == 0 and batch <= num_cu * 2)):
+        return "split"
+    if l <= 32768 and knob >= 0:
+        ks = knob
+        if ks not in (1, 2, 4, 8, 16):
+            waves1 = -(-batch * (d // 4) // 64)
+            ks = 1
+            while ks < 16 and waves1 * ks < num_cu * 8:
+                ks <<= 1
+        while ks > 1 and l // ks < 8:
+            ks >>= 1
+        return ("sliced", ks)
+    return "kernel"
+
+
 KEYGEN_WAVES, VERIFY_WAVES = 4, 4
 
 
