@@ -50,7 +50,9 @@ class WideContext:
                 if len(tab) < self.degree:
                     raise IndexError("list index out of range")
                 self._tables[inverse] = (c_uint64 * self.degree)(*[int(v) % modulus for v in tab[:self.degree]])
-        self._n_inv = pow(self.degree, -1, modulus) if self._tables and np.gcd(self.degree, modulus) == 1 else 0
+        # the final scaling factor of the inverse transform is the reference's own expression, n^(q-2) mod q (ntt.py:353): n^-1 for
+        # every prime q, and what the int32 contexts and both oracles compute for composite q too
+        self._n_inv = pow(self.degree, modulus - 2, modulus) if self._tables else 0
 
     # -- transforms ------------------------------------------------------------------------------------------------------
     def _rows(self, a):

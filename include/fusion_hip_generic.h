@@ -20,8 +20,10 @@ extern "C" {
 #endif
 
 /* h_table: `degree` residues in [0, q), used exactly as the reference uses its `bit_rev_root_powers` /
- * `bit_rev_inv_root_powers` argument (entry m + i for block i of the stage with m blocks); n_inv: degree^{-1} mod q (inverse
- * only).  At most 2^31 - 1 rows per call. */
+ * `bit_rev_inv_root_powers` argument (entry m + i for block i of the stage with m blocks).  n_inv (inverse only): the final
+ * scaling factor, taken from the caller as it is -- every output of the inverse loop nest is multiplied by it.  The library's own
+ * faces pass the reference's expression degree^(q-2) mod q (algebra/ntt.py:353), which is degree^{-1} for a prime q and is NOT for a
+ * composite one.  Table entries and n_inv at or above q are reduced mod q.  At most 2^31 - 1 rows per call. */
 FZ_API int fz_wide_ntt_host(int device, uint64_t q, int degree, const uint64_t *h_table, uint64_t n_inv, int inverse,
                             const int64_t *h_in, int64_t *h_out, size_t batch);
 /* op as for fz_pw_binary_host (0 mul, 1 add, 2 sub, 3 neg); neg returns -(x mod q) in [-(q-1), 0] as the reference's __neg__ does */

@@ -10,30 +10,9 @@ import pytest
 
 from oracle import oracle as O
 
+from _wide_edges import is_prime
+
 pytestmark = pytest.mark.gpu
-
-
-def is_prime(n):
-    """deterministic Miller-Rabin for n < 2^64"""
-    if n < 2:
-        return False
-    for p in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
-        if n % p == 0:
-            return n == p
-    d, s = n - 1, 0
-    while d % 2 == 0:
-        d, s = d // 2, s + 1
-    for a in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
-        x = pow(a, d, n)
-        if x in (1, n - 1):
-            continue
-        for _ in range(s - 1):
-            x = x * x % n
-            if x == n - 1:
-                break
-        else:
-            return False
-    return True
 
 
 def prime_near(start, step, down=False):
