@@ -8,6 +8,7 @@ Two faces:
 """
 import collections
 import ctypes
+import math
 from ctypes import byref, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 import numpy as np
@@ -538,8 +539,11 @@ class Context:
 
 
     # -- host face of the fused scheme cores (object API of fusion.fusion) -----------------------
-    def _staged(self, arrays):
-        return [DeviceBuffer.from_numpy(self, _as_i32(a)) for a in arrays]
+    def _staged(self, scope, arrays):
+        return [scope.own(DeviceBuffer.from_numpy(self, _as_i32(a))) for a in arrays]
+
+    def _scratch(self, scope, nbytes):
+        return scope.own(DeviceBuffer(self, nbytes))
 
     def keygen_core(self, A, coef):
         """A [l][d]; coef [batch][2][l][d] -> (sk_hat [batch][2][l][d], vk [batch][2][d])."""
@@ -547,15 +551,11 @@ class Context:
         l, d = A.shape
         c4 = coef.reshape(-1, 2, l, d)
         batch = c4.shape[0]
-        dA, dC = self._staged([A, c4])
-        dS = DeviceBuffer(self, c4.nbytes)
-        dV = DeviceBuffer(self, batch * 2 * d * 4)
-        try:
+        with DeviceScope() as s:
+            dA, dC = self._staged(s, [A, c4])
+            dS, dV = self._scratch(s, c4.nbytes), self._scratch(s, batch * 2 * d * 4)
             self.keygen_core_dev(dA.ptr, dC.ptr, dS.ptr, dV.ptr, batch, l)
             return dS.to_numpy(np.int32, c4.shape), dV.to_numpy(np.int32, (batch, 2, d))
-        finally:
-            for b in (dA, dC, dS, dV):
-                b.free()
 
     def keygen_core_bcast(self, A, polys):
         """A [l][d]; polys [batch][2][d]: ONE secret polynomial per (key, half), standing for all l rows of that half
@@ -564,28 +564,21 @@ class Context:
         l, d = A.shape
         p3 = polys.reshape(-1, 2, d)
         batch = p3.shape[0]
-        dA, dC = self._staged([A, p3])
-        dS = DeviceBuffer(self, batch * 2 * l * d * 4)
-        dV = DeviceBuffer(self, batch * 2 * d * 4)
-        try:
+        with DeviceScope() as s:
+            dA, dC = self._staged(s, [A, p3])
+            dS, dV = self._scratch(s, batch * 2 * l * d * 4), self._scratch(s, batch * 2 * d * 4)
             self.keygen_core_bcast_dev(dA.ptr, dC.ptr, dS.ptr, dV.ptr, batch, l)
             return dS.to_numpy(np.int32, (batch, 2, l, d)), dV.to_numpy(np.int32, (batch, 2, d))
-        finally:
-            for b in (dA, dC, dS, dV):
-                b.free()
 
     def sign_core(self, sk_hat, c_hat):
         """sk_hat [batch][2][l][d]; c_hat [batch][d] -> sig [batch][l][d]."""
         sk, c = _as_i32(sk_hat), _as_i32(c_hat)
         batch, _, l, d = sk.shape
-        dK, dC = self._staged([sk, c.reshape(batch, d)])
-        dS = DeviceBuffer(self, batch * l * d * 4)
-        try:
+        with DeviceScope() as s:
+            dK, dC = self._staged(s, [sk, c.reshape(batch, d)])
+            dS = self._scratch(s, batch * l * d * 4)
             self.sign_core_dev(dK.ptr, dC.ptr, dS.ptr, batch, l)
             return dS.to_numpy(np.int32, (batch, l, d))
-        finally:
-            for b in (dK, dC, dS):
-                b.free()
 
     def sign_encoded(self, sk_hat, c_hat, bound):
         """sk_hat [batch][2][l][d]; c_hat [batch][d] -> (data uint8 [batch][l * d * w / 8], codes int32 [batch]): the compact
@@ -593,31 +586,21 @@ class Context:
         sk, c = _as_i32(sk_hat), _as_i32(c_hat)
         batch, _, l, d = sk.shape
         rb = l * d * (2 * int(bound)).bit_length() // 8
-        bufs = []
-        try:
-            for a in (sk, c.reshape(batch, d)):
-                bufs.append(DeviceBuffer.from_numpy(self, a))
-            for nbytes in (batch * rb, batch * 4):
-                bufs.append(DeviceBuffer(self, max(1, nbytes)))
-            dK, dC, dB, dV = bufs
+        with DeviceScope() as s:
+            dK, dC = self._staged(s, [sk, c.reshape(batch, d)])
+            dB, dV = self._scratch(s, max(1, batch * rb)), self._scratch(s, max(1, batch * 4))
             self.sign_encoded_async_dev(dK.ptr, dC.ptr, batch, l, int(bound), dB.ptr, dV.ptr)
             return dB.to_numpy(np.uint8, (batch, rb)), dV.to_numpy(np.int32, (batch,))
-        finally:
-            for b in bufs:
-                b.free()
 
     def aggregate_core(self, sig, alpha_hat):
         """sig [N][l][d]; alpha_hat [N][d] -> [l][d]."""
         sig, al = _as_i32(sig), _as_i32(alpha_hat)
         N, l, d = sig.shape
-        dS, dA = self._staged([sig, al.reshape(N, d)])
-        dO = DeviceBuffer(self, l * d * 4)
-        try:
+        with DeviceScope() as s:
+            dS, dA = self._staged(s, [sig, al.reshape(N, d)])
+            dO = self._scratch(s, l * d * 4)
             self.aggregate_core_dev(dS.ptr, dA.ptr, dO.ptr, N, l)
             return dO.to_numpy(np.int32, (l, d))
-        finally:
-            for b in (dS, dA, dO):
-                b.free()
 
     def verify_core(self, A, sig, vkL, vkR, c_hat, alpha_hat, beta_vf, omega_vf):
         """-> verdict code (VERDICT_REASONS)."""
@@ -625,12 +608,9 @@ class Context:
         l, d = A.shape
         vkL, vkR, c_hat, alpha_hat = (_as_i32(x).reshape(-1, d) for x in (vkL, vkR, c_hat, alpha_hat))
         N = vkL.shape[0]
-        bufs = self._staged([A, sig.reshape(l, d), vkL, vkR, c_hat, alpha_hat])
-        try:
-            return self.verify_core_dev(*(b.ptr for b in bufs), N, l, int(beta_vf), int(omega_vf))
-        finally:
-            for b in bufs:
-                b.free()
+        with DeviceScope() as s:
+            staged = self._staged(s, [A, sig.reshape(l, d), vkL, vkR, c_hat, alpha_hat])
+            return self.verify_core_dev(*(b.ptr for b in staged), N, l, int(beta_vf), int(omega_vf))
 
 
 def comm_unique_id():
@@ -747,7 +727,11 @@ class DeviceBuffer:
     def from_numpy(cls, ctx, arr):
         arr = np.ascontiguousarray(arr)
         buf = cls(ctx, arr.nbytes)
-        ctx.h2d(buf.ptr, arr)
+        try:
+            ctx.h2d(buf.ptr, arr)
+        except BaseException:
+            buf.free()
+            raise
         return buf
 
     def to_numpy(self, dtype, shape):
@@ -773,14 +757,18 @@ class DeviceArray:
 
     def __init__(self, ctx, shape, dtype=np.int32):
         self.ctx, self.shape, self.dtype = ctx, tuple(int(x) for x in shape), np.dtype(dtype)
-        self.buf = DeviceBuffer(ctx, max(1, int(np.prod(self.shape)) * self.dtype.itemsize))
+        self.buf = DeviceBuffer(ctx, max(1, math.prod(self.shape) * self.dtype.itemsize))
 
     @classmethod
     def from_numpy(cls, ctx, arr):
         arr = np.ascontiguousarray(arr)
         out = cls(ctx, arr.shape, arr.dtype)
-        if arr.size:
-            ctx.h2d(out.buf.ptr, arr)
+        try:
+            if arr.size:
+                ctx.h2d(out.buf.ptr, arr)
+        except BaseException:
+            out.free()
+            raise
         return out
 
     @property
@@ -793,6 +781,31 @@ class DeviceArray:
 
     def free(self):
         self.buf.free()
+
+
+class DeviceScope:
+    """Owns device temporaries (anything with .free()) for the length of a `with` block: what own() was given is freed on the
+    way out, newest first and each once, on the normal and on the exception path alike -- never by the garbage collector at a
+    time and on a thread of its choosing.  release() takes a buffer out again: a result handed to the caller."""
+    __slots__ = ("_owned",)
+
+    def __init__(self):
+        self._owned = []
+
+    def own(self, buf):
+        self._owned.append(buf)
+        return buf
+
+    def release(self, buf):
+        self._owned.remove(buf)
+        return buf
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        while self._owned:
+            self._owned.pop().free()
 
 
 _CTX_CACHE = {}

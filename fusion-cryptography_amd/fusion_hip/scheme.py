@@ -11,7 +11,7 @@ import numpy as np
 
 from . import hostpipe
 from ._lib import FZ_E_BADARG, FZ_E_UNSUPPORTED, FusionHipError
-from .context import (Context, DeviceArray, ENCODING_REASONS, SIGNATURE_REASONS, VERDICT_REASONS,  # noqa: F401 (re-exported)
+from .context import (Context, DeviceArray, DeviceScope, ENCODING_REASONS, SIGNATURE_REASONS, VERDICT_REASONS,  # noqa: F401 (re-exported)
                       get_context)
 
 # The bound of ONE honest signature, ||INTT(sigma)||_inf <= beta_sk * (1 + min(degree, omega_ch) * CH_BD): the reference's
@@ -149,13 +149,36 @@ class BatchScheme:
             self.ctx.close()
             self.ctx = None
 
-    # ---- keygen ------------------------------------------------------------------------------------
+    # ---- device temporaries ------------------------------------------------------------------------------
+    # Every method that allocates device memory does so inside ONE `with DeviceScope() as s`: what it uploads or allocates is
+    # the scope's from the moment it exists and is freed on the way out, whatever raised; a result that stays on the device is
+    # release()d to the caller.  Helpers that make buffers for their caller take that scope.
     def _dev(self, a, shape):
         """numpy array or DeviceArray -> (DeviceArray, owned?)"""
         if isinstance(a, DeviceArray):
             return a, False
         return DeviceArray.from_numpy(self.ctx, np.ascontiguousarray(a, dtype=np.int32).reshape(shape)), True
 
+    def _take(self, scope, a, shape):
+        """_dev into `scope`: an upload made here is the scope's, a caller's DeviceArray stays the caller's"""
+        return a if isinstance(a, DeviceArray) else scope.own(self._dev(a, shape)[0])
+
+    def _new(self, scope, shape, dtype=np.int32):
+        return scope.own(DeviceArray(self.ctx, shape, dtype))
+
+    def _up(self, scope, arr):
+        return scope.own(DeviceArray.from_numpy(self.ctx, arr))
+
+    def _records_dev(self, scope, data, n, rb):
+        """the second half of _records_input: its n records [n][rb] on the device, uploaded into `scope` unless they are there"""
+        return data if isinstance(data, DeviceArray) else self._up(scope, data.reshape(n, rb))
+
+    @staticmethod
+    def _check_dev(a, shape):
+        if isinstance(a, DeviceArray) and (a.shape != shape or a.dtype != np.int32):
+            raise FusionHipError(FZ_E_BADARG, f"device array {a.shape} {a.dtype}: {shape} int32 expected")
+
+    # ---- keygen ------------------------------------------------------------------------------------
     def keygen_batch(self, seeds, device=False, keep_vk=False):
         """-> (sk_hat [N][2][l][d], vk [N][2][d]); key i equals keygen(params, seeds[i]).  With device=True
         sk_hat stays in device memory (a DeviceArray) -- vk always comes back (hash_ag hashes it on the host); with
@@ -171,50 +194,29 @@ class BatchScheme:
         # non-negative seeds below 2^64 - 1
         # (keygen seeds the right half with seed + 1: for a negative seed that is abs(seed) - 1, not abs(seed) + 1)
         sd = _seed_array(seeds)
-        if sd is None:
-            return self._keygen_batch_python_sampler(seeds, device, keep_vk)
-        n = sd.size
         # the reference's sampler yields ONE polynomial per (key, half) for all l rows (same seed for every matrix
         # entry): 2 KiB per key instead of 166 KiB.  Sampled on the device (an exact MT19937 per lane, fz_sample.hip) when
         # the parameter set allows (weight bound = degree), else by the C clone on the host threads and uploaded.
-        coef = None
-        if self.device_sampler:
-            coef = DeviceArray(self.ctx, (n, 2, self.d))
-            try:
-                self.ctx.sample_secret_polys_dev(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, coef.ptr)
-            except FusionHipError as e:
-                coef.free()
-                coef = None
-                if e.code != FZ_E_UNSUPPORTED:
-                    raise
-                self.device_sampler = False
-        if coef is None:
-            polys = hostpipe.sample_secret_polys(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, self.threads)   # [N][2][d]
-            coef = DeviceArray.from_numpy(self.ctx, polys)
-        dA = self._A_dev()
-        sk = DeviceArray(self.ctx, (n, 2, self.l, self.d))
-        vk = DeviceArray(self.ctx, (n, 2, self.d))
-        try:
-            self.ctx.keygen_core_bcast_dev(dA.ptr, coef.ptr, sk.ptr, vk.ptr, n, self.l)
-            vk_host = vk.numpy()
-            res_sk = sk
-            if not device:
-                res_sk = sk.numpy()
-                sk.free()
-            if keep_vk:
-                keep, vk = vk, None
-                return res_sk, vk_host, keep
-            return res_sk, vk_host
-        finally:
-            for b in (coef, vk):
-                if b is not None:
-                    b.free()
+        with DeviceScope() as s:
+            polys = None
+            if sd is None:
+                polys = self._python_sampler(seeds)
+            elif self.device_sampler:
+                polys = self._new(s, (sd.size, 2, self.d))
+                try:
+                    self.ctx.sample_secret_polys_dev(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, polys.ptr)
+                except FusionHipError as e:
+                    if e.code != FZ_E_UNSUPPORTED:
+                        raise
+                    self.device_sampler, polys = False, None
+            if polys is None:
+                polys = hostpipe.sample_secret_polys(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, self.threads)   # [N][2][d]
+            return self._keygen_from_polys(s, polys, device, keep_vk)
 
-    def _keygen_batch_python_sampler(self, seeds, device, keep_vk):
-        """keygen_batch for seeds the C / device MT19937 clones do not take (negative seeds, where seed + 1 is not
-        abs(seed) + 1, and seeds >= 2^64 - 1, whose keys have more words than the clones' two): the secret polynomials come
-        from the drop-in's own sampler, i.e. CPython's `random` exactly as the reference drives it (polynomials.py:436-467);
-        everything after the sampling is the same device path."""
+    def _python_sampler(self, seeds):
+        """the secret polynomials [N][2][d] for seeds the C / device MT19937 clones do not take (negative seeds, where seed + 1
+        is not abs(seed) + 1, and seeds >= 2^64 - 1, whose keys have more words than the clones' two): from the drop-in's own
+        sampler, i.e. CPython's `random` exactly as the reference drives it (polynomials.py:436-467)"""
         from algebra.polynomials import sample_polynomial_coefficient_representation as sample
         p = self.params
         polys = np.empty((len(seeds), 2, self.d), dtype=np.int32)
@@ -222,97 +224,61 @@ class BatchScheme:
             for h in (0, 1):
                 polys[i, h] = sample(modulus=p.modulus, degree=p.degree, root_order=p.root_order, root=p.root, inv_root=p.inv_root,
                                      norm_bound=p.beta_sk, weight_bound=p.omega_sk, seed=int(s) + h).coefficients
-        n = len(seeds)
-        coef = DeviceArray.from_numpy(self.ctx, polys)
-        sk, vk = DeviceArray(self.ctx, (n, 2, self.l, self.d)), DeviceArray(self.ctx, (n, 2, self.d))
-        try:
-            self.ctx.keygen_core_bcast_dev(self._A_dev().ptr, coef.ptr, sk.ptr, vk.ptr, n, self.l)
-            vk_host = vk.numpy()
-            res_sk = sk
-            if not device:
-                res_sk = sk.numpy()
-                sk.free()
-            if keep_vk:
-                keep, vk = vk, None
-                return res_sk, vk_host, keep
-            return res_sk, vk_host
-        finally:
-            for b in (coef, vk):
-                if b is not None:
-                    b.free()
+        return polys
+
+    def _keygen_from_polys(self, s, polys, device, keep_vk):
+        """keygen_batch after the sampling, the same for every sampler: polys [N][2][d], a host array or a DeviceArray of the
+        caller's -> what keygen_batch returns; temporaries in the scope `s`"""
+        n = polys.shape[0]
+        coef = self._take(s, polys, (n, 2, self.d))
+        dA = self._A_dev()
+        sk, vk = self._new(s, (n, 2, self.l, self.d)), self._new(s, (n, 2, self.d))
+        self.ctx.keygen_core_bcast_dev(dA.ptr, coef.ptr, sk.ptr, vk.ptr, n, self.l)
+        vk_host = vk.numpy()
+        res_sk = s.release(sk) if device else sk.numpy()
+        return (res_sk, vk_host, s.release(vk)) if keep_vk else (res_sk, vk_host)
 
     # ---- sign --------------------------------------------------------------------------------------
-    def challenges_dev(self, vk, messages, want_prehash=True):
+    def challenges_dev(self, vk, messages, want_prehash=True, scope=None):
         """hash_ch for every (key, message) ON THE DEVICE (fz_challenge_hat_msgs_dev: SHA3-256 of the messages, text of
         str(vk), SHAKE-256, decoder, forward NTT): -> (c_hat DeviceArray [N][d], prehash [N][32] or None).  vk: numpy
         [N][2][d] or a DeviceArray of that shape.  Raises FusionHipError(FZ_E_UNSUPPORTED) for parameter sets the device
-        pipeline does not cover."""
+        pipeline does not cover.  c_hat is the caller's to free; with `scope` it is that DeviceScope's, as is an upload of vk."""
+        if scope is None:
+            with DeviceScope() as tmp:
+                dC, pre = self.challenges_dev(vk, messages, want_prehash, tmp)
+                return tmp.release(dC), pre
         blob, off = hostpipe._pack_messages(messages)
         n = len(messages)
-        dV, own = self._dev(vk, (n, 2, self.d))
-        dC = DeviceArray(self.ctx, (n, self.d))
+        dV = self._take(scope, vk, (n, 2, self.d))
+        dC = self._new(scope, (n, self.d))
         try:
             pre = self.ctx.challenge_msgs_dev(self.P, dV.ptr, blob, off, n, dC.ptr, want_prehash)
-        except Exception:
-            dC.free()
-            raise
         finally:
-            if own:
-                self.ctx.synchronize()
-                dV.free()
+            if dV is not vk:
+                self.ctx.synchronize()                      # the launch has read the uploaded keys before they can go
         return dC, pre
 
     def challenges(self, vk, messages):
         """hash_ch for every (key, message): -> (c_hat [N][d], prehash [N][32]).  The per-signer pipeline runs on the
         device when it covers the parameter set (self.device_hash), else in the C host pipeline."""
-        if self.device_hash:
-            try:
-                dC, pre = self.challenges_dev(vk, messages)
-                out = dC.numpy()
-                dC.free()
-                return out, pre
-            except FusionHipError as e:
-                if e.code != FZ_E_UNSUPPORTED:
-                    raise
-                self.device_hash = False
-        vk = np.ascontiguousarray(vk.numpy() if isinstance(vk, DeviceArray) else vk, dtype=np.int32).reshape(-1, 2, self.d)
-        coefs, pre = hostpipe.challenge_coefficients(self.P, np.ascontiguousarray(vk[:, 0]),
-                                                     np.ascontiguousarray(vk[:, 1]), messages, self.threads)
-        return self.ctx.ntt_forward(coefs), pre
-
-    def _challenges_for_signing(self, vk, messages):
-        """the challenge pass of sign_batch and sign_batch_encoded: -> c_hat DeviceArray [N][d] from the device pipeline, or
-        from the host pipeline where the device one does not cover the parameter set"""
-        if self.device_hash:
-            try:
-                return self.challenges_dev(vk, messages, want_prehash=False)[0]
-            except FusionHipError as e:
-                if e.code != FZ_E_UNSUPPORTED:
-                    raise
-                self.device_hash = False
-        c_hat, _ = self.challenges(vk, messages)
-        return DeviceArray.from_numpy(self.ctx, c_hat)
+        with DeviceScope() as s:
+            return self._challenges_both(vk, messages, scope=s, want_dev=False)[1:]
 
     def sign_batch(self, sk_hat, vk, messages, device=False):
         """-> sig [N][l][d]; row i equals sign(params, key_i, messages[i]).signature_hat.
         sk_hat may be a numpy array or a DeviceArray; with device=True the signatures stay on the device.
         With the device challenge pipeline the challenges never visit the host."""
-        dC = self._challenges_for_signing(vk, messages)
-        n = dC.shape[0]
-        dK, own = self._dev(sk_hat, (n, 2, self.l, self.d))
-        dS = DeviceArray(self.ctx, (n, self.l, self.d))
-        try:
+        with DeviceScope() as s:
+            dC = self._challenges_both(vk, messages, want_host=False, scope=s)[0]
+            n = dC.shape[0]
+            dK = self._take(s, sk_hat, (n, 2, self.l, self.d))
+            dS = self._new(s, (n, self.l, self.d))
             self.ctx.sign_core_dev(dK.ptr, dC.ptr, dS.ptr, n, self.l)
             if device:
                 self.ctx.synchronize()
-                return dS
-            out = dS.numpy()
-            dS.free()
-            return out
-        finally:
-            dC.free()
-            if own:
-                dK.free()
+                return s.release(dS)
+            return dS.numpy()
 
     def sign_batch_encoded(self, sk_hat, vk, messages, device=False):
         """sign_batch straight to the compact bytes: -> (data uint8 [N][encoded_size(params,
@@ -339,25 +305,13 @@ class BatchScheme:
             raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} rows of sk_hat")
         if n == 0:
             return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
-        dC = self._challenges_for_signing(vk, messages)
-        bufs = [dC]
-        try:
-            dK, own = self._dev(sk_hat, (n, 2, self.l, self.d))
-            if own:
-                bufs.append(dK)
-            dB = DeviceArray(self.ctx, (n, rb), np.uint8)
-            bufs.append(dB)
-            dV = DeviceArray(self.ctx, (n,))
-            bufs.append(dV)
+        with DeviceScope() as s:
+            dC = self._challenges_both(vk, messages, want_host=False, scope=s)[0]
+            dK = self._take(s, sk_hat, (n, 2, self.l, self.d))
+            dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
             self.ctx.sign_encoded_async_dev(dK.ptr, dC.ptr, n, self.l, bound, dB.ptr, dV.ptr)
             codes = dV.numpy()
-            if device:
-                bufs.remove(dB)                             # the caller's from here
-                return dB, codes
-            return dB.numpy(), codes
-        finally:
-            for b in bufs:
-                b.free()
+            return (s.release(dB) if device else dB.numpy()), codes
 
     # ---- aggregate / verify ----------------------------------------------------------------------------
     def _split_vk(self, vk):
@@ -367,20 +321,30 @@ class BatchScheme:
     def _signer_count(self, vk):
         return vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
 
-    def _challenges_both(self, vk, messages, want_host=True):
+    def _challenges_both(self, vk, messages, want_host=True, scope=None, want_dev=True):
         """hash_ch for every (key, message) in the CALLERS' order: -> (dC DeviceArray [N][d], c_hat host copy, prehash
-        [N][32]).  The device pipeline leaves c_hat where the kernels need it; hash_ag needs a host copy of it as text input
-        (want_host=False, no hash_ag behind the call: the device pipeline downloads neither, None for both)."""
+        [N][32]).  THE place of the rule "the device pipeline where it covers the parameter set, else the C host pipeline"
+        (FZ_E_UNSUPPORTED from the device once, and self.device_hash stays off).  The device pipeline leaves c_hat where the
+        kernels need it; hash_ag needs a host copy of it as text input (want_host=False, no hash_ag behind the call: the
+        device pipeline downloads neither, None for both).  want_dev=False (challenges()): nothing stays on the device, None
+        for dC, and the host pipeline uploads nothing.  dC is the caller's to free (dist.HipSteps), or with `scope` that
+        DeviceScope's."""
+        if scope is None:
+            with DeviceScope() as tmp:
+                dC, c_hat, pre = self._challenges_both(vk, messages, want_host, tmp, want_dev)
+                return (tmp.release(dC) if want_dev else None), c_hat, pre
         if self.device_hash:
             try:
-                dC, pre = self.challenges_dev(vk, messages, want_prehash=want_host)
-                return dC, (dC.numpy() if want_host else None), pre
+                dC, pre = self.challenges_dev(vk, messages, want_host, scope)
+                return (dC if want_dev else None), (dC.numpy() if want_host else None), pre
             except FusionHipError as e:
                 if e.code != FZ_E_UNSUPPORTED:
                     raise
                 self.device_hash = False
-        c_hat, pre = self.challenges(vk, messages)
-        return DeviceArray.from_numpy(self.ctx, c_hat), c_hat, pre
+        _, L, R = self._split_vk(vk)
+        coefs, pre = hostpipe.challenge_coefficients(self.P, L, R, messages, self.threads)
+        c_hat = self.ctx.ntt_forward(coefs)
+        return (self._up(scope, c_hat) if want_dev else None), c_hat, pre
 
     def _sort_async(self, L, R):
         """sort_by_vk_string on a worker thread (the C call releases the GIL): it needs only the keys, so it runs beside the
@@ -396,66 +360,64 @@ class BatchScheme:
         order).  The aggregate and the target are sums over signers, so nothing else ever has to be permuted."""
         return screened_alpha_coefficients(self.P, L, R, pre, c_hat, None, threads or self.threads, order)
 
-    def _aggregate_valid(self, valid, L, R, pre, c_hat, order, sig=None, encoded=None):
+    def _alpha_hat(self, scope, alpha):
+        """coefficient rows [N][d] -> alpha_hat in `scope`: one upload, the forward transform in place (a zero row stays zero)"""
+        dAl = self._up(scope, alpha)
+        self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, alpha.shape[0])
+        return dAl
+
+    def _aggregate_valid(self, scope, valid, L, R, pre, c_hat, order, sig=None, encoded=None):
         """the shared tail of the screened aggregations: hash_ag over the signers with valid[i] set (zero coefficient rows for the
         rest, so nothing is compacted), upload, forward transform in place, one aggregation launch, download: -> aggregate [l][d].
         From the rows `sig` [N][l][d], or from encoded = (dB, dV): the "signature" records on the device and its own verdict
         words, nonzero for the rest, which the fused pass takes as they are for its skip words: a rejected record is not read."""
         _, alpha = screened_alpha_coefficients(self.P, L, R, pre, c_hat, valid, self.threads, order)
         n = alpha.shape[0]
-        dAl, dO = DeviceArray.from_numpy(self.ctx, alpha), DeviceArray(self.ctx, (self.l, self.d))
-        bufs = [dAl, dO]
-        try:
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                       # in place; a zero row stays zero
-            if encoded is None:
-                dS, own = self._dev(sig, (n, self.l, self.d))
-                bufs += [dS] if own else []
-                self.ctx.aggregate_core_dev(dS.ptr, dAl.ptr, dO.ptr, n, self.l)
-            else:
-                dP = DeviceArray(self.ctx, (self.l, self.d), np.int64)
-                bufs.append(dP)
-                bound = _encoding(self.params, "signature")[2]
-                self.ctx.aggregate_encoded_async_dev(encoded[0].ptr, dAl.ptr, encoded[1].ptr, n, self.l, bound, dP.ptr, dO.ptr)
-            return dO.numpy()
-        finally:
-            for b in bufs:
-                b.free()
+        dO, dAl = self._new(scope, (self.l, self.d)), self._alpha_hat(scope, alpha)
+        if encoded is None:
+            dS = self._take(scope, sig, (n, self.l, self.d))
+            self.ctx.aggregate_core_dev(dS.ptr, dAl.ptr, dO.ptr, n, self.l)
+        else:
+            dP = self._new(scope, (self.l, self.d), np.int64)
+            bound = _encoding(self.params, "signature")[2]
+            self.ctx.aggregate_encoded_async_dev(encoded[0].ptr, dAl.ptr, encoded[1].ptr, n, self.l, bound, dP.ptr, dO.ptr)
+        return dO.numpy()
 
-    def hash_ag_dev(self, vk, messages):
-        """Everything aggregate() and verify() derive from the keys and messages, device-resident and in the callers' order:
-        -> (dC [N][d] challenges c_hat, dAl [N][d] aggregation coefficients alpha_hat, order, vkL, vkR host rows)."""
+    def _hash_ag_host(self, vk, messages, scope, keep_c=True):
+        """the keys' and messages' share of one hash_ag, with the key sort on its worker beside the challenge pass (neither
+        needs the other): -> (dC, c_hat, pre, order, L, R); keep_c=False: c_hat does not stay on the device, None for dC"""
         vk, L, R = self._split_vk(vk)
-        order_f = self._sort_async(L, R)                    # beside the challenge pipeline: neither needs the other
+        order_f = self._sort_async(L, R)
         try:
-            dC, c_hat, pre = self._challenges_both(vk, messages)
-        except Exception:
-            order_f.result()
-            raise
-        try:
-            order, alpha = self._alpha_coefficients(L, R, pre, c_hat, order=order_f.result())
-            dAl = DeviceArray.from_numpy(self.ctx, alpha)
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, alpha.shape[0])          # in place
-        except Exception:
-            dC.free()
-            raise
-        return dC, dAl, order, L, R
+            with DeviceScope() as tmp:                      # keep_c=False: c_hat leaves the device once its host copy is here
+                dC, c_hat, pre = self._challenges_both(vk, messages, scope=scope if keep_c else tmp)
+        finally:
+            order = order_f.result()
+        return (dC if keep_c else None), c_hat, pre, order, L, R
+
+    def hash_ag_dev(self, vk, messages, scope=None):
+        """Everything aggregate() and verify() derive from the keys and messages, device-resident and in the callers' order:
+        -> (dC [N][d] challenges c_hat, dAl [N][d] aggregation coefficients alpha_hat, order, vkL, vkR host rows).  dC and dAl
+        are the caller's to free, or with `scope` that DeviceScope's."""
+        if scope is None:
+            with DeviceScope() as tmp:
+                dC, dAl, order, L, R = self.hash_ag_dev(vk, messages, tmp)
+                return tmp.release(dC), tmp.release(dAl), order, L, R
+        dC, c_hat, pre, order, L, R = self._hash_ag_host(vk, messages, scope)
+        order, alpha = self._alpha_coefficients(L, R, pre, c_hat, order=order)
+        return dC, self._alpha_hat(scope, alpha), order, L, R
 
     def aggregate(self, vk, messages, sig):
         """-> aggregate [l][d] == aggregate(params, keys, messages, signatures).signature_hat.
         sig may be a numpy array or a DeviceArray.  Challenges and aggregation coefficients stay on the device; only the
         keys' text input of hash_ag and the result cross PCIe."""
-        dC, dAl, _, _, _ = self.hash_ag_dev(vk, messages)
-        n = dAl.shape[0]
-        dS, own = self._dev(sig, (n, self.l, self.d))
-        dO = DeviceArray(self.ctx, (self.l, self.d))
-        try:
+        with DeviceScope() as s:
+            dC, dAl, _, _, _ = self.hash_ag_dev(vk, messages, scope=s)
+            n = dAl.shape[0]
+            dS = self._take(s, sig, (n, self.l, self.d))
+            dO = self._new(s, (self.l, self.d))
             self.ctx.aggregate_core_dev(dS.ptr, dAl.ptr, dO.ptr, n, self.l)
             return dO.numpy()
-        finally:
-            for b in (dC, dAl, dO):
-                b.free()
-            if own:
-                dS.free()
 
     def aggregate_verify(self, vk, messages, sig):
         """aggregate() followed by verify() of the result on the same keys and messages, as an aggregator that checks its own
@@ -465,28 +427,60 @@ class BatchScheme:
         from .dist import LocalCollective, ShardedScheme
         return ShardedScheme(self, 0, 1, LocalCollective(self.ctx)).aggregate_verify_sharded(vk, messages, sig)
 
-    def verify(self, vk, messages, aggregate):
-        """-> (bool, reason) with the reference's reason strings (fusion.py:680-728)"""
-        n = self._signer_count(vk)
+    # ---- the steps the four verify forms share ------------------------------------------------------------
+    def _refused(self, n, messages):
+        """the verdicts that need no arithmetic, capacity first (fusion.py:686-689): -> (False, reason), or None to go on"""
         if n > self.params.capacity:
             return False, VERDICT_REASONS[1]
         if n != len(messages):
             return False, VERDICT_REASONS[2]
-        dC, dAl, _, L, R = self.hash_ag_dev(vk, messages)
-        dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
-        dS, own = self._dev(aggregate, (self.l, self.d))
-        try:
-            code = self.ctx.verify_core_dev(self._A_dev().ptr, dS.ptr, dL.ptr, dR.ptr, dC.ptr, dAl.ptr, n, self.l,
-                                            int(self.params.beta_vf), int(self.params.omega_vf))
-            return code == 0, VERDICT_REASONS[code]
-        finally:
-            for b in (dC, dAl, dL, dR):
-                b.free()
-            if own:
-                dS.free()
+        return None
+
+    def _one_by_one(self, single, vk, messages, items, shape, sizes):
+        """verify_many / verify_many_encoded when some group is over capacity (rare; it keeps the batch path simple): that
+        group's verdict is the capacity one, the others are verified one by one by single(vk_g, messages_g, items_g);
+        -> the verdicts, or None when every group is within capacity"""
+        live = [i for i, n in enumerate(sizes) if n <= self.params.capacity]
+        if len(live) == len(sizes):
+            return None
+        out = [(False, VERDICT_REASONS[1])] * len(sizes)
+        vkh, _, _ = self._split_vk(vk)
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        items = (items.numpy() if isinstance(items, DeviceArray) else np.asarray(items)).reshape((len(sizes),) + shape)
+        for i in live:
+            out[i] = single(vkh[off[i]:off[i + 1]], messages[off[i]:off[i + 1]], items[i])
+        return out
+
+    def _target(self, scope, dL, dR, dC, dAl, n):
+        """the verification target of ONE aggregate of n signers, centred: -> dT [d]"""
+        dT64, dT = self._new(scope, (self.d,), np.int64), self._new(scope, (self.d,))
+        self.ctx.target_partial_dev(dL.ptr, dR.ptr, dC.ptr, dAl.ptr, dT64.ptr, n)
+        self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, self.d)
+        return dT
+
+    def _targets(self, scope, dL, dR, dC, dAl, off):
+        """the verification targets of the len(off) - 1 aggregates of rows off[g]:off[g+1], one launch, centred: -> dT [G][d]"""
+        g = len(off) - 1
+        dT64, dT = self._new(scope, (g, self.d), np.int64), self._new(scope, (g, self.d))
+        self.ctx.aggregate_target_partial_ragged_dev(0, dAl.ptr, dL.ptr, dR.ptr, dC.ptr, off, self.l, 0, 0, dT64.ptr, self.d)
+        self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, g * self.d)
+        return dT
+
+    def verify(self, vk, messages, aggregate):
+        """-> (bool, reason) with the reference's reason strings (fusion.py:680-728)"""
+        n = self._signer_count(vk)
+        refused = self._refused(n, messages)
+        if refused is not None:
+            return refused
+        with DeviceScope() as s:
+            dC, dAl, _, L, R = self.hash_ag_dev(vk, messages, scope=s)
+            dL, dR = self._up(s, L), self._up(s, R)
+            dS = self._take(s, aggregate, (self.l, self.d))
+            return _verdict(self.ctx.verify_core_dev(self._A_dev().ptr, dS.ptr, dL.ptr, dR.ptr, dC.ptr, dAl.ptr, n, self.l,
+                                                     int(self.params.beta_vf), int(self.params.omega_vf)))
 
     # ---- one signature at a time (not in the reference) ----------------------------------------------------
-    def _screen(self, vk, messages, sig, beta, omega, want_hash_ag):
+    def _screen(self, vk, messages, sig, beta, omega, want_hash_ag, scope):
         """the per-signature verdicts of N signers, -> (codes [N] int32, c_hat host copy, prehash), the last two None unless
         want_hash_ag.  One challenge pass, one launch, one verdict download; vk is uploaded once (the challenge pipeline reads
         the same copy)."""
@@ -497,24 +491,16 @@ class BatchScheme:
         omega = int(self.params.omega_vf) if omega is None else int(omega)
         if beta < 0 or omega < 0:
             raise FusionHipError(FZ_E_BADARG, f"bounds must be non-negative (beta={beta}, omega={omega})")
-        for a, shape in ((vk, (n, 2, self.d)), (sig, (n, self.l, self.d))):
-            if isinstance(a, DeviceArray) and (a.shape != shape or a.dtype != np.int32):
-                raise FusionHipError(FZ_E_BADARG, f"device array {a.shape} {a.dtype}: {shape} int32 expected")
+        self._check_dev(vk, (n, 2, self.d))
+        self._check_dev(sig, (n, self.l, self.d))
         if n == 0:
             return np.zeros(0, dtype=np.int32), None, None
-        dK, own = self._dev(vk, (n, 2, self.d))
-        bufs = [dK] if own else []
-        try:
-            dC, c_hat, pre = self._challenges_both(dK, messages, want_hash_ag)
-            bufs.append(dC)
-            dS, own = self._dev(sig, (n, self.l, self.d))
-            dV = DeviceArray(self.ctx, (n,))
-            bufs += [dS, dV] if own else [dV]
-            self.ctx.verify_signatures_async_dev(self._A_dev().ptr, dS.ptr, dK.ptr, dC.ptr, n, self.l, beta, omega, dV.ptr)
-            return (dV.numpy(), c_hat, pre) if want_hash_ag else (dV.numpy(), None, None)
-        finally:
-            for b in bufs:
-                b.free()
+        dK = self._take(scope, vk, (n, 2, self.d))
+        dC, c_hat, pre = self._challenges_both(dK, messages, want_hash_ag, scope=scope)
+        dS = self._take(scope, sig, (n, self.l, self.d))
+        dV = self._new(scope, (n,))
+        self.ctx.verify_signatures_async_dev(self._A_dev().ptr, dS.ptr, dK.ptr, dC.ptr, n, self.l, beta, omega, dV.ptr)
+        return (dV.numpy(), c_hat, pre) if want_hash_ag else (dV.numpy(), None, None)
 
     def verify_signatures(self, vk, messages, sig, beta=None, omega=None):
         """Per-signature verification (not a reference function): -> int32 codes [N], 0 where signer i's signature is valid
@@ -524,7 +510,8 @@ class BatchScheme:
         3172 at 256; a params object of another secpar must pass it), omega to params.omega_vf.  vk [N][2][d] and sig
         [N][l][d] may be numpy arrays or DeviceArrays (keygen_batch(..., keep_vk=True) / sign_batch(..., device=True)).
         Unequal numbers of keys and messages raise FusionHipError(FZ_E_BADARG): a caller error, not a verdict."""
-        return self._screen(vk, messages, sig, beta, omega, False)[0]
+        with DeviceScope() as s:
+            return self._screen(vk, messages, sig, beta, omega, False, s)[0]
 
     def aggregate_screened(self, vk, messages, sig):
         """aggregate() over the signers whose signature passes verify_signatures, for aggregators that take untrusted
@@ -532,12 +519,14 @@ class BatchScheme:
         aggregate(vk[ok], messages[ok], sig[ok]) -- one bad contribution no longer spoils the aggregate, and the codes say
         whose it was.  One challenge pass serves both steps; hash_ag runs over the valid signers only, its coefficients are
         scattered back with zero rows for the rejected ones, so the signature rows are never compacted."""
-        codes, c_hat, pre = self._screen(vk, messages, sig, None, None, True)
+        with DeviceScope() as s:                            # of its own: the screen's copy of sig goes before the aggregation's comes
+            codes, c_hat, pre = self._screen(vk, messages, sig, None, None, True, s)
         valid = codes == 0
         if not valid.any():
             return None, codes
         _, L, R = self._split_vk(vk)
-        return self._aggregate_valid(valid, L, R, pre, c_hat, None, sig=sig), codes
+        with DeviceScope() as s:
+            return self._aggregate_valid(s, valid, L, R, pre, c_hat, None, sig=sig), codes
 
     # ---- compact byte encoding (not in the reference; INTEGRATION.md section G) ------------------------------------
     def encode(self, kind, rows):
@@ -557,15 +546,11 @@ class BatchScheme:
         n = int(shape[0])
         if n == 0:
             return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
-        dR, own = self._dev(rows, (n, nrows, self.d))
-        dB, dV = DeviceArray(self.ctx, (n, rb), np.uint8), DeviceArray(self.ctx, (n,))
-        bufs = [dR, dB, dV] if own else [dB, dV]
-        try:
+        with DeviceScope() as s:
+            dR = self._take(s, rows, (n, nrows, self.d))
+            dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
             self.ctx.encode_records_async_dev(dR.ptr, n, nrows, coef, bound, dB.ptr, dV.ptr)
             return dB.numpy(), dV.numpy()
-        finally:
-            for b in bufs:
-                b.free()
 
     def decode(self, kind, data, device=False):
         """-> (rows, codes int32 [N]): the records of `data` (bytes, bytearray, memoryview, a uint8 numpy array or a uint8
@@ -578,19 +563,22 @@ class BatchScheme:
         if n == 0:
             empty = np.zeros((0, nrows, self.d), dtype=np.int32)
             return (DeviceArray.from_numpy(self.ctx, empty) if device else empty), np.zeros(0, dtype=np.int32)
-        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
-        dR, dV = DeviceArray(self.ctx, (n, nrows, self.d)), DeviceArray(self.ctx, (n,))
-        bufs = [dR, dV] if dB is data else [dB, dR, dV]
-        try:
+        with DeviceScope() as s:
+            dB = self._records_dev(s, data, n, rb)
+            dR, dV = self._new(s, (n, nrows, self.d)), self._new(s, (n,))
             self.ctx.decode_records_async_dev(dB.ptr, n, nrows, coef, bound, dR.ptr, dV.ptr)
             codes = dV.numpy()
-            if device:
-                bufs.remove(dR)                              # the caller's from here
-                return dR, codes
-            return dR.numpy(), codes
-        finally:
-            for b in bufs:
-                b.free()
+            return (s.release(dR) if device else dR.numpy()), codes
+
+    def _signature_records(self, vk, messages, data):
+        """the byte input of the calls that take one "signature" record per signer, refused with FusionHipError(FZ_E_BADARG)
+        unless it is whole records and as many as there are keys and messages: -> (nrows, bound, rb, data, n)"""
+        nrows, _, bound, _, rb = _encoding(self.params, "signature")
+        data, n = _records_input("signature", data, rb)
+        nk = self._signer_count(vk)
+        if not (nk == len(messages) == n):
+            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
+        return nrows, bound, rb, data, n
 
     def aggregate_encoded(self, vk, messages, data):
         """aggregate() straight from the signatures' compact bytes (`data`: N "signature" records in every form decode
@@ -605,65 +593,41 @@ class BatchScheme:
         (verify); when that fails, aggregate_encoded_screened on the same bytes names the signer.
         A length that is not N whole records, or numbers of keys / messages other than N, raise FusionHipError(FZ_E_BADARG)
         before the device is touched."""
-        nrows, _, bound, _, rb = _encoding(self.params, "signature")
-        data, n = _records_input("signature", data, rb)
-        nk = self._signer_count(vk)
-        if not (nk == len(messages) == n):
-            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
+        nrows, bound, rb, data, n = self._signature_records(vk, messages, data)
         if n == 0:
             return None, np.zeros(0, dtype=np.int32)
-        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
-        dV = DeviceArray(self.ctx, (n,))
-        bufs = [dV] if dB is data else [dB, dV]
-        try:
+        with DeviceScope() as s:
+            dB = self._records_dev(s, data, n, rb)
+            dV = self._new(s, (n,))
             self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
-            vk, L, R = self._split_vk(vk)
-            order_f = self._sort_async(L, R)                # beside the check and the challenge pipeline
-            try:
-                dC, c_hat, pre = self._challenges_both(vk, messages)
-                dC.free()                                   # hash_ag reads the host copy; nothing here needs c_hat on the device
-            finally:
-                order = order_f.result()
+            # beside the check; hash_ag reads the host copy of c_hat, nothing here needs it on the device
+            _, c_hat, pre, order, L, R = self._hash_ag_host(vk, messages, s, keep_c=False)
             codes = dV.numpy()
             valid = codes == 0
             if not valid.any():
                 return None, codes
-            return self._aggregate_valid(valid, L, R, pre, c_hat, order, encoded=(dB, dV)), codes
-        finally:
-            for b in bufs:
-                b.free()
+            return self._aggregate_valid(s, valid, L, R, pre, c_hat, order, encoded=(dB, dV)), codes
 
     # ---- verification straight from the bytes (not in the reference; INTEGRATION.md section G) ---------------------
     def _screen_encoded(self, vk, messages, data, aggregate):
         """verify_signatures_encoded, and with aggregate=True the screened aggregation behind it: -> (aggregate or None,
         codes).  The argument checks come before anything touches the device."""
-        nrows, _, bound, _, rb = _encoding(self.params, "signature")
-        data, n = _records_input("signature", data, rb)
-        nk = self._signer_count(vk)
-        if not (nk == len(messages) == n):
-            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} records")
-        if isinstance(vk, DeviceArray) and (vk.shape != (n, 2, self.d) or vk.dtype != np.int32):
-            raise FusionHipError(FZ_E_BADARG, f"device array {vk.shape} {vk.dtype}: {(n, 2, self.d)} int32 expected")
+        _, bound, rb, data, n = self._signature_records(vk, messages, data)
+        self._check_dev(vk, (n, 2, self.d))
         if n == 0:
             return None, np.zeros(0, dtype=np.int32)
-        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
-        bufs = [] if dB is data else [dB]
-        try:
-            dK, own = self._dev(vk, (n, 2, self.d))
-            dV = DeviceArray(self.ctx, (n,))
-            bufs += [dK, dV] if own else [dV]
-            dC, c_hat, pre = self._challenges_both(dK, messages, aggregate)
-            bufs.append(dC)
+        with DeviceScope() as s:
+            dB = self._records_dev(s, data, n, rb)
+            dK = self._take(s, vk, (n, 2, self.d))
+            dV = self._new(s, (n,))
+            dC, c_hat, pre = self._challenges_both(dK, messages, aggregate, scope=s)
             self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
             codes = dV.numpy()
             valid = codes == 0
             if not aggregate or not valid.any():
                 return None, codes
             _, L, R = self._split_vk(vk)
-            return self._aggregate_valid(valid, L, R, pre, c_hat, None, encoded=(dB, dV)), codes
-        finally:
-            for b in bufs:
-                b.free()
+            return self._aggregate_valid(s, valid, L, R, pre, c_hat, None, encoded=(dB, dV)), codes
 
     def verify_signatures_encoded(self, vk, messages, data):
         """verify_signatures straight from the signatures' compact bytes (`data`: N "signature" records in every form decode
@@ -694,127 +658,90 @@ class BatchScheme:
         if nrec != 1:
             raise FusionHipError(FZ_E_BADARG, f"{nrec} 'aggregate' records: exactly one expected")
         n = self._signer_count(vk)
-        if n > self.params.capacity:
-            return False, VERDICT_REASONS[1]
-        if n != len(messages):
-            return False, VERDICT_REASONS[2]
-        dC, dAl, _, L, R = self.hash_ag_dev(vk, messages)
-        bufs = [dC, dAl]
-        try:
-            dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
-            bufs += [dL, dR]
-            dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(1, rb))
-            bufs += [] if dB is data else [dB]
-            dT64, dT, dV = DeviceArray(self.ctx, (self.d,), np.int64), DeviceArray(self.ctx, (self.d,)), DeviceArray(self.ctx, (1,))
-            bufs += [dT64, dT, dV]
-            self.ctx.target_partial_dev(dL.ptr, dR.ptr, dC.ptr, dAl.ptr, dT64.ptr, n)
-            self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, self.d)
+        refused = self._refused(n, messages)
+        if refused is not None:
+            return refused
+        with DeviceScope() as s:
+            dC, dAl, _, L, R = self.hash_ag_dev(vk, messages, scope=s)
+            dL, dR = self._up(s, L), self._up(s, R)
+            dB = self._records_dev(s, data, 1, rb)
+            dV, dT = self._new(s, (1,)), self._target(s, dL, dR, dC, dAl, n)
             self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, 1, self.l, bound, dT.ptr, 0, 0, dV.ptr)
-            code = int(dV.numpy()[0])
-            return code == 0, (ENCODING_REASONS[6] if code == 6 else VERDICT_REASONS[code])
-        finally:
-            for b in bufs:
-                b.free()
+            return _verdict(dV.numpy()[0])
 
     # ---- many aggregates at once ------------------------------------------------------------------------
-    def _hash_ag_many(self, vk, messages, sizes):
-        """hash_ag for G independent aggregates whose signers are concatenated (aggregate g = rows off[g]:off[g+1]): ONE device
-        pass for all challenges, then one host thread per aggregate for its sort + serial SHAKE-256 (the sponges are what
-        bounds a lone aggregate: independent aggregates hide each other's), ONE upload + transform of all coefficients.
-        -> (dC, dAl [sum N][d], offsets, L, R)"""
-        from concurrent.futures import ThreadPoolExecutor
-        vk, L, R = self._split_vk(vk)
-        sizes = [int(x) for x in sizes]
-        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        if off[-1] != vk.shape[0] or vk.shape[0] != len(messages):
-            raise FusionHipError(-1, f"sizes sum to {off[-1]} but {vk.shape[0]} keys and {len(messages)} messages were given")
-        if any(x < 1 for x in sizes):
-            raise FusionHipError(-1, "every aggregate needs at least one signer")
-        dC, c_hat, pre = self._challenges_both(vk, messages)
-        try:
-            per = max(1, self.threads // max(1, len(sizes)))
-
-            def one(g):
-                a, b = off[g], off[g + 1]
-                return self._alpha_coefficients(L[a:b], R[a:b], pre[a:b], c_hat[a:b], per)[1]
-            with ThreadPoolExecutor(max_workers=min(len(sizes), self.threads)) as pool:      # the C calls release the GIL
-                alpha = np.concatenate(list(pool.map(one, range(len(sizes)))))
-            dAl = DeviceArray.from_numpy(self.ctx, alpha)
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, alpha.shape[0])
-        except Exception:
-            dC.free()
-            raise
-        return dC, dAl, off, L, R
-
-    def aggregate_many(self, vk, messages, sig, sizes):
-        """G independent aggregate() calls (fusion.py:655; the reference is called once per aggregate) as one batch:
-        vk [sum N][2][d], messages (sum N of them), sig [sum N][l][d] (numpy or DeviceArray) hold the signers of aggregate 0,
-        then of aggregate 1, ...; sizes = signers per aggregate (they may differ).  -> [G][l][d]; row g equals
-        aggregate(params, keys_g, messages_g, signatures_g).signature_hat.  One launch for all aggregates."""
-        dC, dAl, off, _, _ = self._hash_ag_many(vk, messages, sizes)
-        g = len(off) - 1
-        dS, own = self._dev(sig, (int(off[-1]), self.l, self.d))
-        dO = DeviceArray(self.ctx, (g, self.l, self.d))
-        try:
-            self.ctx.aggregate_core_ragged_dev(dS.ptr, dAl.ptr, off, self.l, dO.ptr)
-            return dO.numpy()
-        finally:
-            for b in (dC, dAl, dO):
-                b.free()
-            if own:
-                dS.free()
-
-    def verify_many(self, vk, messages, aggregates, sizes):
-        """G independent verify() calls (fusion.py:680-728) as one batch; aggregates [G][l][d].  -> list of (bool, reason).
-        One launch for all verification targets, one for all verifications, verdicts read once."""
-        sizes = [int(x) for x in sizes]
-        g = len(sizes)
-        out = [None] * g
-        live = []
-        for i, n in enumerate(sizes):                 # the reference's capacity check comes first (fusion.py:686-687)
-            if n > self.params.capacity:
-                out[i] = (False, VERDICT_REASONS[1])
-            else:
-                live.append(i)
-        if len(live) != g:                            # rare: verify the rest one by one, keeping the batch path simple
-            vkh, _, _ = self._split_vk(vk)
-            off = np.concatenate([[0], np.cumsum(sizes)])
-            aggs = aggregates.numpy() if isinstance(aggregates, DeviceArray) else np.asarray(aggregates)
-            for i in live:
-                out[i] = self.verify(vkh[off[i]:off[i + 1]], messages[off[i]:off[i + 1]], aggs.reshape(g, self.l, self.d)[i])
-            return out
-        dC, dAl, off, L, R = self._hash_ag_many(vk, messages, sizes)
-        dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
-        dS, own = self._dev(aggregates, (g, self.l, self.d))
-        dT64 = DeviceArray(self.ctx, (g, self.d), np.int64)
-        dT = DeviceArray(self.ctx, (g, self.d))
-        dV = DeviceArray(self.ctx, (g,))
-        try:
-            self.ctx.aggregate_target_partial_ragged_dev(0, dAl.ptr, dL.ptr, dR.ptr, dC.ptr, off, self.l, 0, 0, dT64.ptr, self.d)
-            self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, g * self.d)
-            self.ctx.verify_with_target_batch_async_dev(self._A_dev().ptr, dS.ptr, dT.ptr, g, self.l, int(self.params.beta_vf),
-                                                        int(self.params.omega_vf), dV.ptr)
-            return [(int(c) == 0, VERDICT_REASONS[int(c)]) for c in dV.numpy()]
-        finally:
-            for b in (dC, dAl, dL, dR, dT64, dT, dV):
-                b.free()
-            if own:
-                dS.free()
-
-    # ---- many aggregates at once, straight from the bytes (not in the reference; INTEGRATION.md section G) ---------
     def _many_sizes(self, vk, messages, sizes):
-        """sizes as ints, refused with FusionHipError(FZ_E_BADARG) unless each is at least 1 and they sum to the numbers of keys
-        and of messages; no device is touched"""
+        """sizes as ints, refused with FusionHipError(FZ_E_BADARG) unless each is at least 1 and they sum to the numbers of keys and
+        of messages; no device is touched"""
         sizes = [int(x) for x in sizes]
         if any(x < 1 for x in sizes):
             raise FusionHipError(FZ_E_BADARG, "every aggregate needs at least one signer")
         nk = self._signer_count(vk)
         if not (sum(sizes) == nk == len(messages)):
             raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {nk} keys and {len(messages)} messages were given")
-        if isinstance(vk, DeviceArray) and (vk.shape != (nk, 2, self.d) or vk.dtype != np.int32):
-            raise FusionHipError(FZ_E_BADARG, f"device array {vk.shape} {vk.dtype}: {(nk, 2, self.d)} int32 expected")
         return sizes
 
+    def _alpha_hat_many(self, scope, off, L, R, pre, c_hat, valid=None):
+        """hash_ag's coefficients for the G = len(off) - 1 independent aggregates of rows off[g]:off[g+1], over the signers with
+        valid[i] set (None: all): one host thread per aggregate for its sort + serial SHAKE-256 (the sponges are what bounds a
+        lone aggregate: independent aggregates hide each other's), zero rows without hashing for a group with no valid signer,
+        then ONE upload + transform of all rows: -> dAl [sum N][d] in `scope`"""
+        from concurrent.futures import ThreadPoolExecutor
+        g = len(off) - 1
+        per = max(1, self.threads // max(1, g))
+
+        def one(k):
+            a, b = off[k], off[k + 1]
+            ok = None if valid is None else valid[a:b]
+            if ok is not None and not ok.any():
+                return np.zeros((b - a, self.d), dtype=np.int32)
+            return screened_alpha_coefficients(self.P, L[a:b], R[a:b], pre[a:b], c_hat[a:b], ok, per)[1]
+        with ThreadPoolExecutor(max_workers=min(g, self.threads)) as pool:      # the C calls release the GIL
+            alpha = np.concatenate(list(pool.map(one, range(g))))
+        return self._alpha_hat(scope, alpha)
+
+    def _hash_ag_many(self, scope, vk, messages, sizes):
+        """hash_ag for G independent aggregates whose signers are concatenated (aggregate g = rows off[g]:off[g+1]; sizes as
+        _many_sizes passed them): ONE device pass for all challenges, _alpha_hat_many.  -> (dC, dAl [sum N][d], offsets, L, R),
+        the buffers in `scope`"""
+        vk, L, R = self._split_vk(vk)
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        dC, c_hat, pre = self._challenges_both(vk, messages, scope=scope)
+        return dC, self._alpha_hat_many(scope, off, L, R, pre, c_hat), off, L, R
+
+    def aggregate_many(self, vk, messages, sig, sizes):
+        """G independent aggregate() calls (fusion.py:655; the reference is called once per aggregate) as one batch:
+        vk [sum N][2][d], messages (sum N of them), sig [sum N][l][d] (numpy or DeviceArray) hold the signers of aggregate 0,
+        then of aggregate 1, ...; sizes = signers per aggregate (they may differ).  -> [G][l][d]; row g equals
+        aggregate(params, keys_g, messages_g, signatures_g).signature_hat.  One launch for all aggregates."""
+        sizes = self._many_sizes(vk, messages, sizes)
+        with DeviceScope() as s:
+            dC, dAl, off, _, _ = self._hash_ag_many(s, vk, messages, sizes)
+            g = len(off) - 1
+            dS = self._take(s, sig, (int(off[-1]), self.l, self.d))
+            dO = self._new(s, (g, self.l, self.d))
+            self.ctx.aggregate_core_ragged_dev(dS.ptr, dAl.ptr, off, self.l, dO.ptr)
+            return dO.numpy()
+
+    def verify_many(self, vk, messages, aggregates, sizes):
+        """G independent verify() calls (fusion.py:680-728) as one batch; aggregates [G][l][d].  -> list of (bool, reason).
+        One launch for all verification targets, one for all verifications, verdicts read once."""
+        sizes = [int(x) for x in sizes]
+        g = len(sizes)
+        out = self._one_by_one(self.verify, vk, messages, aggregates, (self.l, self.d), sizes)   # the capacity check comes first
+        if out is not None:
+            return out
+        sizes = self._many_sizes(vk, messages, sizes)
+        with DeviceScope() as s:
+            dC, dAl, off, L, R = self._hash_ag_many(s, vk, messages, sizes)
+            dL, dR = self._up(s, L), self._up(s, R)
+            dS = self._take(s, aggregates, (g, self.l, self.d))
+            dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, dC, dAl, off)
+            self.ctx.verify_with_target_batch_async_dev(self._A_dev().ptr, dS.ptr, dT.ptr, g, self.l, int(self.params.beta_vf),
+                                                        int(self.params.omega_vf), dV.ptr)
+            return [_verdict(c) for c in dV.numpy()]
+
+    # ---- many aggregates at once, straight from the bytes (not in the reference; INTEGRATION.md section G) ---------
     def aggregate_many_encoded(self, vk, messages, data, sizes, screened=False, encoded=False):
         """G independent aggregate_encoded calls (screened=True: aggregate_encoded_screened calls) as one batch: vk [sum N][2][d]
         (numpy or DeviceArray), messages and `data` (sum N "signature" records in every form decode takes) hold the signers of
@@ -830,11 +757,11 @@ class BatchScheme:
         one download.  Sizes that do not sum to the numbers of records, keys and messages, a size below 1, or a length that is
         not whole records raise FusionHipError(FZ_E_BADARG) before the device is touched; no records and sizes == [] return
         empty arrays without a device."""
-        from concurrent.futures import ThreadPoolExecutor
         nrows, _, bound, _, rb = _encoding(self.params, "signature")
         _, _, abound, _, arb = _encoding(self.params, "aggregate")
         data, n = _records_input("signature", data, rb)
         sizes = self._many_sizes(vk, messages, sizes)
+        self._check_dev(vk, (sum(sizes), 2, self.d))
         if sum(sizes) != n:
             raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {n} records were given")
         g = len(sizes)
@@ -843,49 +770,28 @@ class BatchScheme:
             return (np.zeros((0, arb), dtype=np.uint8), codes, np.zeros(0, dtype=np.int32)) if encoded else \
                 (np.zeros((0, self.l, self.d), dtype=np.int32), codes)
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(n, rb))
-        bufs = [] if dB is data else [dB]
-        try:
-            dV = DeviceArray(self.ctx, (n,))
-            bufs.append(dV)
+        with DeviceScope() as s:
+            dB = self._records_dev(s, data, n, rb)
+            dV = self._new(s, (n,))
             if screened:
-                dK, own = self._dev(vk, (n, 2, self.d))
-                bufs += [dK] if own else []
-                dC, c_hat, pre = self._challenges_both(dK, messages)
-                bufs.append(dC)
+                dK = self._take(s, vk, (n, 2, self.d))
+                dC, c_hat, pre = self._challenges_both(dK, messages, scope=s)
                 self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
             else:
                 self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
             _, L, R = self._split_vk(vk)
             if not screened:
-                dC, c_hat, pre = self._challenges_both(vk, messages)
-                dC.free()                                   # hash_ag reads the host copy; nothing here needs c_hat on the device
+                with DeviceScope() as t:                    # hash_ag reads the host copy; nothing here needs c_hat on the device
+                    _, c_hat, pre = self._challenges_both(vk, messages, scope=t)
             codes = dV.numpy()
-            valid = codes == 0
-            per = max(1, self.threads // g)
-
-            def one(k):
-                a, b = off[k], off[k + 1]
-                if not valid[a:b].any():
-                    return np.zeros((b - a, self.d), dtype=np.int32)
-                return screened_alpha_coefficients(self.P, L[a:b], R[a:b], pre[a:b], c_hat[a:b], valid[a:b], per)[1]
-            with ThreadPoolExecutor(max_workers=min(g, self.threads)) as pool:      # the C calls release the GIL
-                alpha = np.concatenate(list(pool.map(one, range(g))))
-            dAl = DeviceArray.from_numpy(self.ctx, alpha)
-            bufs.append(dAl)
-            self.ctx.ntt_forward_dev(dAl.ptr, dAl.ptr, n)                           # in place; a zero row stays zero
-            dP, dO = DeviceArray(self.ctx, (g, self.l, self.d), np.int64), DeviceArray(self.ctx, (g, self.l, self.d))
-            bufs += [dP, dO]
+            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, codes == 0)
+            dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
             self.ctx.aggregate_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, off, self.l, bound, dP.ptr, self.l * self.d, dO.ptr)
             if not encoded:
                 return dO.numpy(), codes
-            dR, dW = DeviceArray(self.ctx, (g, arb), np.uint8), DeviceArray(self.ctx, (g,))
-            bufs += [dR, dW]
+            dR, dW = self._new(s, (g, arb), np.uint8), self._new(s, (g,))
             self.ctx.encode_records_async_dev(dO.ptr, g, self.l, True, abound, dR.ptr, dW.ptr)
             return dR.numpy(), codes, dW.numpy()
-        finally:
-            for b in bufs:
-                b.free()
 
     def verify_many_encoded(self, vk, messages, data, sizes):
         """G independent verify_encoded calls as one batch: `data` holds G "aggregate" records (every form decode takes), vk and
@@ -898,36 +804,29 @@ class BatchScheme:
         _, _, bound, _, rb = _encoding(self.params, "aggregate")
         data, nrec = _records_input("aggregate", data, rb)
         sizes = self._many_sizes(vk, messages, sizes)
+        self._check_dev(vk, (sum(sizes), 2, self.d))
         g = len(sizes)
         if nrec != g:
             raise FusionHipError(FZ_E_BADARG, f"{nrec} 'aggregate' records but {g} sizes")
         if g == 0:
             return []
-        live = [i for i, n in enumerate(sizes) if n <= self.params.capacity]
-        if len(live) != g:                            # rare, as in verify_many: the capacity check first, the rest one by one
-            out = [(False, VERDICT_REASONS[1])] * g
-            vkh, _, _ = self._split_vk(vk)
-            off = np.concatenate([[0], np.cumsum(sizes)])
-            recs = (data.numpy() if isinstance(data, DeviceArray) else data).reshape(g, rb)
-            for i in live:
-                out[i] = self.verify_encoded(vkh[off[i]:off[i + 1]], messages[off[i]:off[i + 1]], recs[i])
+        out = self._one_by_one(self.verify_encoded, vk, messages, data, (rb,), sizes)      # the capacity check first, as in verify_many
+        if out is not None:
             return out
-        dC, dAl, off, L, R = self._hash_ag_many(vk, messages, sizes)
-        bufs = [dC, dAl]
-        try:
-            dL, dR = DeviceArray.from_numpy(self.ctx, L), DeviceArray.from_numpy(self.ctx, R)
-            bufs += [dL, dR]
-            dB = data if isinstance(data, DeviceArray) else DeviceArray.from_numpy(self.ctx, data.reshape(g, rb))
-            bufs += [] if dB is data else [dB]
-            dT64, dT, dV = DeviceArray(self.ctx, (g, self.d), np.int64), DeviceArray(self.ctx, (g, self.d)), DeviceArray(self.ctx, (g,))
-            bufs += [dT64, dT, dV]
-            self.ctx.aggregate_target_partial_ragged_dev(0, dAl.ptr, dL.ptr, dR.ptr, dC.ptr, off, self.l, 0, 0, dT64.ptr, self.d)
-            self.ctx.reduce_i64_dev(dT64.ptr, dT.ptr, g * self.d)
+        with DeviceScope() as s:
+            dC, dAl, off, L, R = self._hash_ag_many(s, vk, messages, sizes)
+            dL, dR = self._up(s, L), self._up(s, R)
+            dB = self._records_dev(s, data, g, rb)
+            dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, dC, dAl, off)
             self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, g, self.l, bound, dT.ptr, 0, 0, dV.ptr)
-            return [(int(c) == 0, ENCODING_REASONS[6] if int(c) == 6 else VERDICT_REASONS[int(c)]) for c in dV.numpy()]
-        finally:
-            for b in bufs:
-                b.free()
+            return [_verdict(c) for c in dV.numpy()]
+
+
+def _verdict(code):
+    """a verification's code -> (ok, reason): the reference's reason strings, and for a record that is not canonical (6, from
+    the bytes only) the encoding's"""
+    code = int(code)
+    return code == 0, (ENCODING_REASONS[6] if code == 6 else VERDICT_REASONS[code])
 
 
 def _seed_array(seeds):
