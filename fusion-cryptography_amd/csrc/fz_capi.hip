@@ -449,6 +449,23 @@ int fz_sign_encoded_async(fz_ctx *ctx, const int32_t *d_sk_hat, const int32_t *d
     return fz_launch_sign_encoded(ctx, d_sk_hat, d_c_hat, N, l, w, bound, d_bytes, d_status);
 }
 
+// the same from the key's "secret" record: z = INTT(NTT(sL) * c_hat) + sR, the right half added in the coefficient domain
+// (fusion/fusion.py:534-557 by linearity), and its encoding in one pass: neither the key's nor the signature's rows reach memory.
+// fz_sign_encoded_async's checks in its order; the key's bound is held to the output bound's range
+int fz_sign_records_async(fz_ctx *ctx, const uint8_t *d_key_bytes, int64_t key_bound, const int32_t *d_c_hat, size_t N, int l,
+                          int64_t bound, uint8_t *d_bytes, int *d_status) {
+    int w = 0, wk = 0;
+    const char *ptrs_wrong = records_ptrs(d_key_bytes, d_bytes, d_status);
+    if (!ptrs_wrong) ptrs_wrong = records_ptrs(d_c_hat, d_c_hat, d_c_hat);
+    FZ_REQUIRE(ctx && l >= 1, "bad argument");
+    FZ_REQUIRE(key_bound >= 1 && key_bound <= ((int64_t)ctx->q - 1) / 2, "key bound %lld outside [1, (q-1)/2]", (long long)key_bound);
+    FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
+    if (N == 0) return FZ_OK;
+    while ((2 * key_bound) >> wk) ++wk;
+    FZ_DEV(ctx);
+    return fz_launch_sign_records(ctx, d_key_bytes, wk, key_bound, d_c_hat, N, l, w, bound, d_bytes, d_status);
+}
+
 int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status) {
     int w = 0;
     FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_bytes, d_bytes, d_status), &w));

@@ -84,6 +84,7 @@ struct fz_ctx {
     int grid_aggenc, grid_check; // ... of aggregate_encoded and encoded_check (fz_aggregate_encoded.hip; degree 64 / 256)
     int grid_signenc;            // ... of sign_encode (fz_sign_encoded.hip; degree 64 / 256)
     int grid_aggenc_rag;         // ... of aggregate_encoded_ragged (fz_aggregate_many_encoded.hip; degree 64 / 256)
+    int grid_signrec;            // ... of sign_records (fz_sign_records.hip; degree 64 / 256)
     // verification from the bytes with several workgroups per record (fz_verify_encoded.hip; degree 64 / 256): a slot of int64 sums
     // and a status word per record, venc_bytes in all; allocated once at context creation (fz_verify_encoded_setup), never grown --
     // the entry is allocation-free and capturable from its first call -- and released by fz_ctx_destroy
@@ -287,6 +288,13 @@ int fz_sign_encoded_query_grid(fz_ctx *ctx);                       // ctx->grid_
 int fz_launch_sign_encoded(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat, size_t n, int l, int w, int64_t bound,
                            uint8_t *d_bytes, int *d_status);
 
+// signing straight from "secret" records to the bytes (fz_sign_records.hip; degree 64 / 256): record i of d_bytes = the encoding of
+// cent(INV(cent(FWD(sL_i) (.) c_i)) + sR_i) from key records [n][2][l][degree] of wk-bit fields s + key_bound and c_hat [n][degree], any
+// int32; d_status [n] cleared, then 0, FZ_VERDICT_NORM or FZ_VERDICT_ENCODING (a key field above 2 key_bound); refused records zeroed
+int fz_sign_records_query_grid(fz_ctx *ctx);                       // ctx->grid_signrec (context creation: fz_aggregate_many_encoded_query_grid calls it)
+int fz_launch_sign_records(fz_ctx *ctx, const uint8_t *key_bytes, int wk, int64_t key_bound, const int32_t *c_hat, size_t n, int l,
+                           int w, int64_t bound, uint8_t *d_bytes, int *d_status);
+
 // the byte encoding's consumers without rows (fz_aggregate_encoded.hip; degree 64 / 256): the range check of a byte stream alone
 // (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from
 // their bytes: d_partial [l][degree] int64 zeroed, then sum_i cent(NTT(z_i) (.) alpha_hat_i) over the signers with skip[i] == 0
@@ -300,7 +308,7 @@ int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t
 // of `groups` owns records [h_offsets[g], h_offsets[g + 1]) of the concatenated byte stream and the same rows of alpha and skip;
 // its int64 partial [l][degree] at d_partial + g * pstride is zeroed, then summed as fz_launch_aggregate_encoded does; d_out
 // [groups][l][degree] = cent(partial) when not NULL.  h_offsets is read before the call returns.
-int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx);             // ctx->grid_aggenc_rag (context creation: fz_sign_encoded_query_grid calls it)
+int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx);             // ctx->grid_aggenc_rag, then fz_sign_records_query_grid (context creation: fz_sign_encoded_query_grid calls it)
 int fz_launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const size_t *h_offsets,
                                        size_t groups, int l, int w, int64_t bound, int64_t *d_partial, size_t pstride, int32_t *d_out);
 

@@ -1,7 +1,8 @@
 // fz_records_dev.h -- the device building blocks of the compact byte encoding that more than one unit uses (fz_records.hip: the
 // records_* kernels; fz_aggregate_encoded.hip and fz_aggregate_many_encoded.hip, through fz_aggregate_encoded_dev.h: the range check
 // and the aggregation straight from the bytes, of one committee and of many; fz_verify_encoded.hip:
-// the verification straight from the bytes; fz_sign_encoded.hip: signing straight to the bytes): the packed chunk of the chunk
+// the verification straight from the bytes; fz_sign_encoded.hip: signing straight to the bytes; fz_sign_records.hip: signing
+// straight from the key's bytes to the signature's): the packed chunk of the chunk
 // walk with its loads and stores, the field packing and unpacking, the steps from the packed chunk to the transform's outputs and
 // their sums, the per-record status flag and the record walk.  No kernels and no host code here; everything is private to the
 // unit that includes it.

@@ -551,17 +551,21 @@ def verify_signatures(params: Params, keys: List[OneTimeVerificationKey], messag
 
 
 def to_bytes(params: Params, obj, aggregate: bool = False) -> bytes:
-    """NOT in the reference (an extension of the object face): the canonical compact bytes of a OneTimeVerificationKey or a
-    Signature; aggregate=True encodes a Signature under the aggregate bound beta_vf instead of the
-    single-signature one.  Raises ValueError with the reason when the object cannot be encoded (its norm is over the bound)."""
+    """NOT in the reference (an extension of the object face): the canonical compact bytes of a OneTimeVerificationKey, a
+    OneTimeSigningKey (a "secret" record) or a Signature; aggregate=True encodes a Signature under
+    the aggregate bound beta_vf instead of the single-signature one.  Raises ValueError with the reason when the object cannot
+    be encoded (its norm is over the bound)."""
     from fusion_hip import ENCODING_REASONS
     from fusion_hip.scheme import BatchScheme, signature_from_object, vk_from_object
     if isinstance(obj, OneTimeVerificationKey):
         kind, rows = "vk", vk_from_object(params, obj)[None]
     elif isinstance(obj, Signature):
         kind, rows = ("aggregate" if aggregate else "signature"), signature_from_object(params, obj)[None]
+    elif isinstance(obj, OneTimeSigningKey):
+        q = params.modulus
+        kind, rows = "secret", np.stack([_rows_of(obj.left_sk_hat, q), _rows_of(obj.right_sk_hat, q)])[None]
     else:
-        raise TypeError(f"to_bytes takes a OneTimeVerificationKey or a Signature, not {type(obj).__name__}")
+        raise TypeError(f"to_bytes takes a OneTimeVerificationKey, a OneTimeSigningKey or a Signature, not {type(obj).__name__}")
     bs = BatchScheme(params)
     try:
         data, codes = bs.encode(kind, rows)
@@ -589,11 +593,30 @@ def sign_to_bytes(params: Params, key: OneTimeKeyTuple, message: str) -> bytes:
     return data.tobytes()
 
 
-def from_bytes(params: Params, kind: str, data: bytes):
-    """NOT in the reference: the inverse of to_bytes for one record of `kind` ("vk", "signature" or "aggregate") -> a
-    OneTimeVerificationKey or a Signature.  Raises ValueError for a wrong length or a record that is not canonical."""
+def sign_from_bytes(params: Params, secret_record: bytes, vk: OneTimeVerificationKey, message: str) -> bytes:
+    """NOT in the reference: sign_to_bytes(params, (from_bytes(params, "secret", secret_record), vk), message) without the key's
+    rows in between -- the challenge as sign() takes it, then one fz_sign_records_async call that signs from the record and
+    packs.  Raises ValueError for a record of the wrong length, and with the reason for a record that is not canonical (6) or a
+    signature over the bound of one signature (4)."""
     from fusion_hip import ENCODING_REASONS
-    from fusion_hip.scheme import BatchScheme, encoded_size, signature_to_object, vk_to_object
+    from fusion_hip.scheme import encoded_size, signature_bound
+    size = encoded_size(params, "secret")
+    if len(secret_record) != size:
+        raise ValueError(f"a 'secret' record is {size} bytes, not {len(secret_record)}")
+    c_hat = hash_ch(params=params, key=vk, message=message).c_hat
+    data, codes = _ctx(params).sign_records(bytes(secret_record), int(params.beta_sk), c_hat._i32()[None], params.num_rows_sk,
+                                            signature_bound(params))
+    if codes[0]:
+        raise ValueError(ENCODING_REASONS[int(codes[0])])
+    return data.tobytes()
+
+
+def from_bytes(params: Params, kind: str, data: bytes):
+    """NOT in the reference: the inverse of to_bytes for one record of `kind` ("vk", "signature", "aggregate" or "secret") -> a
+    OneTimeVerificationKey, a Signature or a OneTimeSigningKey (seed=None: the record does not hold it).  Raises ValueError for
+    a wrong length or a record that is not canonical."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import BatchScheme, encoded_size, signature_to_object, sk_to_object, vk_to_object
     size = encoded_size(params, kind)
     if len(data) != size:
         raise ValueError(f"a {kind!r} record is {size} bytes, not {len(data)}")
@@ -604,6 +627,8 @@ def from_bytes(params: Params, kind: str, data: bytes):
         bs.close()
     if codes[0]:
         raise ValueError(ENCODING_REASONS[int(codes[0])])
+    if kind == "secret":
+        return sk_to_object(params, None, rows[0])
     return vk_to_object(params, rows[0]) if kind == "vk" else signature_to_object(params, rows[0])
 
 

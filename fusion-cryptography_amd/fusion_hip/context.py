@@ -413,6 +413,14 @@ class Context:
         check(self._lib, self._lib.fz_sign_encoded_async(self._h, c_void_p(d_sk_hat), c_void_p(d_c_hat), n, l, bound,
                                                          c_void_p(d_bytes), c_void_p(d_status)))
 
+    def sign_records_async_dev(self, d_key_bytes, key_bound, d_c_hat, n, l, bound, d_bytes, d_status):
+        """signing straight from the key's bytes: d_key_bytes holds n "secret" records ([2][l][d] fields s + key_bound, left half
+        first); record i of d_bytes = the encoding under `bound` of cent(INTT(cent(NTT(sL_i) (.) c_i)) + sR_i), exactly what
+        decode_records_async_dev(rows = 2 l, coef) followed by sign_encoded_async_dev leaves, without the int32 rows of either;
+        codes (0, 4, 6: a key field above 2 key_bound comes first) to d_status [n], a refused record's bytes zero (asynchronous)"""
+        check(self._lib, self._lib.fz_sign_records_async(self._h, c_void_p(d_key_bytes), key_bound, c_void_p(d_c_hat), n, l, bound,
+                                                         c_void_p(d_bytes), c_void_p(d_status)))
+
     def decode_records_async_dev(self, d_bytes, n, rows, coef, bound, d_rows, d_status):
         """... and back: codes (0, 6) to d_status [n], a refused record's rows zero (asynchronous)"""
         check(self._lib, self._lib.fz_decode_records_async(self._h, c_void_p(d_bytes), n, rows, 1 if coef else 0, bound,
@@ -590,6 +598,27 @@ class Context:
             dK, dC = self._staged(s, [sk, c.reshape(batch, d)])
             dB, dV = self._scratch(s, max(1, batch * rb)), self._scratch(s, max(1, batch * 4))
             self.sign_encoded_async_dev(dK.ptr, dC.ptr, batch, l, int(bound), dB.ptr, dV.ptr)
+            return dB.to_numpy(np.uint8, (batch, rb)), dV.to_numpy(np.int32, (batch,))
+
+    def sign_records(self, key_bytes, key_bound, c_hat, l, bound):
+        """key_bytes: batch "secret" records of [2][l][d] fields under key_bound (uint8, [batch][2 * l * d * wk / 8] or flat);
+        c_hat [batch][d] -> (data uint8 [batch][l * d * w / 8], codes int32 [batch]): the compact bytes of the signatures under
+        `bound` in one pass (sign_records_async_dev), codes 0, 4 or 6."""
+        c = _as_i32(c_hat)
+        d = c.shape[-1]
+        c = c.reshape(-1, d)
+        batch, l = c.shape[0], int(l)
+        kb = 2 * l * d * (2 * int(key_bound)).bit_length() // 8
+        rb = l * d * (2 * int(bound)).bit_length() // 8
+        key = np.ascontiguousarray(np.frombuffer(key_bytes, dtype=np.uint8) if isinstance(key_bytes, (bytes, bytearray, memoryview))
+                                   else key_bytes)
+        if key.dtype != np.uint8 or key.size != batch * kb:
+            raise FusionHipError(FZ_E_BADARG, f"{key.size} bytes of {key.dtype}: {batch} uint8 records of {kb} bytes expected")
+        with DeviceScope() as s:
+            dK = s.own(DeviceBuffer.from_numpy(self, key.reshape(batch, kb)))
+            dC, = self._staged(s, [c])
+            dB, dV = self._scratch(s, max(1, batch * rb)), self._scratch(s, max(1, batch * 4))
+            self.sign_records_async_dev(dK.ptr, int(key_bound), dC.ptr, batch, l, int(bound), dB.ptr, dV.ptr)
             return dB.to_numpy(np.uint8, (batch, rb)), dV.to_numpy(np.int32, (batch,))
 
     def aggregate_core(self, sig, alpha_hat):

@@ -34,6 +34,8 @@ _ENCODING_KINDS = {
     "vk": lambda p: (2, False, (p.modulus - 1) // 2),
     "signature": lambda p: (p.num_rows_sk, True, signature_bound(p)),
     "aggregate": lambda p: (p.num_rows_sk, True, int(p.beta_vf)),
+    # a signing key's [2][l][d] rows, left half first: |s| <= beta_sk for every key keygen can make (omega_sk = d: no weight bound)
+    "secret": lambda p: (2 * p.num_rows_sk, True, int(p.beta_sk)),
 }
 
 
@@ -48,7 +50,8 @@ def _encoding(params, kind):
 
 
 def encoded_size(params, kind):
-    """bytes of one record of `kind` ("vk", "signature" or "aggregate") in the compact byte encoding; no device needed"""
+    """bytes of one record of `kind` ("vk", "signature", "aggregate" or "secret") in the compact byte encoding; no device
+    needed"""
     return _encoding(params, kind)[4]
 
 
@@ -213,6 +216,31 @@ class BatchScheme:
                 polys = hostpipe.sample_secret_polys(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, self.threads)   # [N][2][d]
             return self._keygen_from_polys(s, polys, device, keep_vk)
 
+    def keygen_batch_encoded(self, seeds, device=False):
+        """keygen_batch straight to "secret" records: -> (records uint8 [N][encoded_size(params,
+        "secret")], vk [N][2][d]); record i is bit for bit encode("secret", keygen_batch(seeds)[0])[0][i] (an honest key is
+        within beta_sk: the codes are all 0, anything else raises FusionHipError).  With device=True the records stay on the
+        device as a uint8 DeviceArray, which sign_batch_records takes as it is.  Deliberately thin: the existing keygen with
+        sk_hat kept on the device, then the encoder on it inside the same scope -- the int32 key is freed on the way out and
+        never downloaded.
+        Seeds that are not a flat sequence of integers raise FusionHipError(FZ_E_BADARG) before the device is touched.  No
+        seeds: empty numpy arrays for either value of `device` (as sign_batch_records: a DeviceArray would need a device)."""
+        nrows, coef, bound, _, rb = _encoding(self.params, "secret")
+        seeds = _integer_seeds(seeds)
+        n = len(seeds)
+        if n == 0:
+            return np.zeros((0, rb), dtype=np.uint8), np.zeros((0, 2, self.d), dtype=np.int32)
+        with DeviceScope() as s:
+            dK, vk = self.keygen_batch(seeds, device=True)
+            s.own(dK)
+            dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
+            self.ctx.encode_records_async_dev(dK.ptr, n, nrows, coef, bound, dB.ptr, dV.ptr)
+            codes = dV.numpy()
+            if codes.any():
+                bad = int(np.flatnonzero(codes)[0])
+                raise FusionHipError(FZ_E_BADARG, f"key {bad}: {ENCODING_REASONS[int(codes[bad])]}")
+            return (s.release(dB) if device else dB.numpy()), vk
+
     def _python_sampler(self, seeds):
         """the secret polynomials [N][2][d] for seeds the C / device MT19937 clones do not take (negative seeds, where seed + 1
         is not abs(seed) + 1, and seeds >= 2^64 - 1, whose keys have more words than the clones' two): from the drop-in's own
@@ -310,6 +338,39 @@ class BatchScheme:
             dK = self._take(s, sk_hat, (n, 2, self.l, self.d))
             dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
             self.ctx.sign_encoded_async_dev(dK.ptr, dC.ptr, n, self.l, bound, dB.ptr, dV.ptr)
+            codes = dV.numpy()
+            return (s.release(dB) if device else dB.numpy()), codes
+
+    def sign_batch_records(self, secret, vk, messages, device=False):
+        """sign_batch_encoded straight from the keys' compact bytes: `secret` holds N "secret" records
+        in every form decode takes (bytes, bytearray, memoryview, a uint8 numpy array or a uint8 DeviceArray, e.g. what
+        keygen_batch_encoded(device=True) returns) -> (data uint8 [N][encoded_size(params, "signature")], codes int32 [N]); for
+        canonical records bit for bit sign_batch_encoded(decode("secret", secret)[0], vk, messages).  data is a numpy array, or
+        with device=True a uint8 DeviceArray; codes are on the host: codes[i] is 6 (ENCODING_REASONS) when key record i is not
+        canonical (a field above 2 beta_sk), and its bytes are then zero.  Code 4 cannot occur with hash_ch's challenges:
+        |z| <= beta_sk (1 + omega_ch) = 1456 / 3172 <= signature_bound at secpar 128 / 256.  The challenge pass is sign_batch's;
+        one fused pass then unpacks the key, transforms the left half, multiplies, transforms back, adds the right half,
+        range-checks and packs: no int32 row of key or signature exists on the device.
+        A length that is not N whole records, or a number of keys or messages other than N, raises
+        FusionHipError(FZ_E_BADARG) before the device is touched.  N == 0 returns empty numpy arrays for either value of
+        `device`, as sign_batch_encoded does: the call then needs no device, which a DeviceArray would (decode, which is
+        given its device by the caller's choice of `device`, returns an empty DeviceArray there)."""
+        _, _, key_bound, _, kb = _encoding(self.params, "secret")
+        _, _, bound, _, rb = _encoding(self.params, "signature")
+        secret, n = _records_input("secret", secret, kb)
+        try:
+            nk = self._signer_count(vk)
+        except ValueError:
+            nk = -1
+        if not (nk == len(messages) == n):
+            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} secret records")
+        if n == 0:
+            return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
+        with DeviceScope() as s:
+            dC = self._challenges_both(vk, messages, want_host=False, scope=s)[0]
+            dK = self._records_dev(s, secret, n, kb)
+            dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
+            self.ctx.sign_records_async_dev(dK.ptr, key_bound, dC.ptr, n, self.l, bound, dB.ptr, dV.ptr)
             codes = dV.numpy()
             return (s.release(dB) if device else dB.numpy()), codes
 
@@ -534,10 +595,13 @@ class BatchScheme:
         [N][2][d]), signatures or aggregates ("signature" / "aggregate", rows [N][l][d]; one [l][d] aggregate is N = 1), as
         numpy arrays or a DeviceArray.  codes[i] is 4 (ENCODING_REASONS) when record i is over its kind's bound -- exactly the
         signatures verify_signatures rejects for the norm, the aggregates verify() rejects for it; keys never are -- and its
-        bytes are then zero."""
+        bytes are then zero.  "secret": the signing keys sk_hat [N][2][l][d] (or [N][2l][d]), left half first, under beta_sk;
+        code 4 means a key the reference's keygen cannot make."""
         nrows, coef, bound, w, rb = _encoding(self.params, kind)
         shape = rows.shape if isinstance(rows, DeviceArray) else np.shape(rows)
-        if kind != "vk" and len(shape) == 2:
+        if kind == "secret" and len(shape) == 4 and tuple(shape[1:]) == (2, self.l, self.d):
+            shape = (shape[0], nrows, self.d)
+        elif kind not in ("vk", "secret") and len(shape) == 2:
             shape = (1,) + tuple(shape)
         if len(shape) != 3 or tuple(shape[1:]) != (nrows, self.d):
             raise FusionHipError(FZ_E_BADARG, f"rows of shape {tuple(shape)}: [N][{nrows}][{self.d}] expected for {kind!r}")
@@ -554,18 +618,19 @@ class BatchScheme:
 
     def decode(self, kind, data, device=False):
         """-> (rows, codes int32 [N]): the records of `data` (bytes, bytearray, memoryview, a uint8 numpy array or a uint8
-        DeviceArray; N * encoded_size(params, kind) bytes) as int32 rows [N][2][d] ("vk") or [N][l][d], NTT domain, centred
-        -- numpy, or a DeviceArray with device=True (straight into verify_signatures / aggregate).  codes[i] is 6
-        (ENCODING_REASONS) when record i is not canonical (a field above 2B), and its rows are then zero.  A length that is not
-        a whole number of records raises FusionHipError(FZ_E_BADARG)."""
+        DeviceArray; N * encoded_size(params, kind) bytes) as int32 rows [N][2][d] ("vk"), [N][2][l][d] ("secret") or [N][l][d],
+        NTT domain, centred -- numpy, or a DeviceArray with device=True (straight into verify_signatures / aggregate).
+        codes[i] is 6 (ENCODING_REASONS) when record i is not canonical (a field above 2B), and its rows are then zero.  A
+        length that is not a whole number of records raises FusionHipError(FZ_E_BADARG)."""
         nrows, coef, bound, w, rb = _encoding(self.params, kind)
         data, n = _records_input(kind, data, rb)
+        shape = (2, self.l, self.d) if kind == "secret" else (nrows, self.d)
         if n == 0:
-            empty = np.zeros((0, nrows, self.d), dtype=np.int32)
+            empty = np.zeros((0,) + shape, dtype=np.int32)
             return (DeviceArray.from_numpy(self.ctx, empty) if device else empty), np.zeros(0, dtype=np.int32)
         with DeviceScope() as s:
             dB = self._records_dev(s, data, n, rb)
-            dR, dV = self._new(s, (n, nrows, self.d)), self._new(s, (n,))
+            dR, dV = self._new(s, (n,) + shape), self._new(s, (n,))
             self.ctx.decode_records_async_dev(dB.ptr, n, nrows, coef, bound, dR.ptr, dV.ptr)
             codes = dV.numpy()
             return (s.release(dR) if device else dR.numpy()), codes
@@ -827,6 +892,25 @@ def _verdict(code):
     the bytes only) the encoding's"""
     code = int(code)
     return code == 0, (ENCODING_REASONS[6] if code == 6 else VERDICT_REASONS[code])
+
+
+def _integer_seeds(seeds):
+    """the seeds as they came when they are a flat sequence of integers (Python or numpy ones, of any sign and size; no
+    booleans), else FusionHipError(FZ_E_BADARG): a float would be truncated and a nested list fail half way otherwise"""
+    if isinstance(seeds, np.ndarray):
+        if seeds.ndim == 1 and (seeds.dtype.kind in "iu" or seeds.size == 0):
+            return seeds
+        raise FusionHipError(FZ_E_BADARG,
+                             f"seeds of shape {seeds.shape} and type {seeds.dtype}: a flat sequence of integers expected")
+    try:
+        seeds = list(seeds)
+    except TypeError:
+        raise FusionHipError(FZ_E_BADARG,
+                             f"seeds of type {type(seeds).__name__}: a flat sequence of integers expected") from None
+    for i, v in enumerate(seeds):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise FusionHipError(FZ_E_BADARG, f"seed {i} is a {type(v).__name__}: a flat sequence of integers expected")
+    return seeds
 
 
 def _seed_array(seeds):

@@ -346,6 +346,23 @@ FZ_API int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n
 FZ_API int fz_sign_encoded_async(fz_ctx *ctx, const int32_t *d_sk_hat, const int32_t *d_c_hat, size_t N, int l, int64_t bound,
                                  uint8_t *d_bytes, int *d_status);
 
+/* signing straight from the key's bytes to the signature's bytes (fusion/fusion.py:534-557 by linearity: INTT(NTT(sL) * c_hat +
+ * NTT(sR)) = INTT(NTT(sL) * c_hat) + sR; neither the key's nor the signature's int32 rows reach memory).  d_key_bytes holds N
+ * "secret" records: [2][l][degree] fields s + key_bound of wk = bit_length(2 * key_bound) bits, left half first, in the format
+ * of fz_encode_records_async (2 * l * degree * wk / 8 bytes each, always a multiple of 16).  With FWD / INV the context's
+ * transforms, record i of d_bytes [N][l * degree * w / 8] holds the fields z + bound of
+ *     z = cent(INV(cent(FWD(sL_i) (.) c_hat_i)) + sR_i)
+ * -- on a context whose tables are a root's, exactly what fz_decode_records_async(rows = 2 l, coef = 1, key_bound) followed by
+ * fz_sign_encoded_async leaves.  d_status[i] = FZ_VERDICT_ENCODING when some field of key record i is above 2 * key_bound (this
+ * comes first), else FZ_VERDICT_NORM when some |z| > bound, else 0; a record with a non-zero status is all zero bytes, the
+ * others are unaffected.  The key bytes and d_c_hat (any int32) are not written.  Rules of fz_sign_encoded_async, in its
+ * order: FZ_E_BADARG for a NULL context, l < 1 or either bound outside [1, (q-1)/2]; N == 0 does nothing and writes nothing;
+ * FZ_E_BADARG for a pointer that is NULL or not 16-byte aligned (all four); FZ_E_UNSUPPORTED for degrees other than 64 and 256;
+ * a stream whose last 16-byte unit is half full ends there.  Asynchronous on the context's stream, allocation-free, capturable
+ * by fz_graph_* (the clear of d_status and the zeroing of refused records are part of the captured work). */
+FZ_API int fz_sign_records_async(fz_ctx *ctx, const uint8_t *d_key_bytes, int64_t key_bound, const int32_t *d_c_hat, size_t N, int l,
+                                 int64_t bound, uint8_t *d_bytes, int *d_status);
+
 /* the range check of fz_decode_records_async alone (no transform, no rows): status per record 0 or FZ_VERDICT_ENCODING (a field
  * > 2 * bound); nothing else is written.  Same arguments and rules as fz_decode_records_async, for either kind of record. */
 FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status);
