@@ -11,21 +11,19 @@ namespace {
 __global__ __launch_bounds__(64 * kWavesPerBlock) void encoded_check(const uint8_t *in, size_t total, unsigned rec_values, int w, int bound,
                                                                      int *status) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock * kPackBytes];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const size_t tasks = (total + kChunk - 1) / kChunk;
+    const int lane = threadIdx.x & 63;
+    const ChunkTasks T(total);
     const size_t total_bytes = total / 8 * (size_t)w;
-    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
-    const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
-    if (first >= tasks) return;                           // (no workgroup-wide barrier in this kernel)
-    uint8_t *pk = lds + wave * kPackBytes;
-    packed_to_lds(pk, packed_load(in, first, total_bytes, w, lane), w, lane);
-    RecWalk walk(first, stride, rec_values, lane);
+    if (T.first >= T.tasks) return;                       // (no workgroup-wide barrier in this kernel)
+    uint8_t *pk = lds + T.wave * kPackBytes;
+    packed_to_lds(pk, packed_load(in, T.first, total_bytes, w, lane), w, lane);
+    RecWalk walk(T.first, T.stride, rec_values, lane);
     const uint32_t two_b = 2u * (unsigned)bound;
 
     auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {       // pipeline and peeling: see fwd16_run
         constexpr bool more = decltype(more_tag)::value;
         Packed raw = {};
-        if (more) raw = packed_load(in, task + stride, total_bytes, w, lane);
+        if (more) raw = packed_load(in, task + T.stride, total_bytes, w, lane);
         wave_sync();
         uint32_t u[16], mx = 0;
         fields_unpack(reinterpret_cast<const uint16_t *>(pk) + lane * w, u, w);
@@ -37,8 +35,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void encoded_check(const uint8
         records_flag(status, walk.rec, mx > two_b && valid, FZ_VERDICT_ENCODING, lane);
         walk.step();
     };
-    size_t task = first;
-    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
+    size_t task = T.first;
+    for (; task + T.stride < T.tasks; task += T.stride) iteration(task, std::true_type());
     iteration(task, std::false_type());
 }
 
@@ -94,10 +92,8 @@ int fz_launch_check_records(fz_ctx *ctx, const uint8_t *bytes, size_t n, int row
     const size_t total = n * rv;
     int rc = fz_check_hip(hipMemsetAsync(d_status, 0, n * sizeof(int), ctx->stream), "records status clear");
     if (rc != FZ_OK) return rc;
-    const size_t tasks = (total + kChunk - 1) / kChunk, blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
-    const size_t cap = (size_t)ctx->grid_check;
-    hipLaunchKernelGGL(encoded_check, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(64 * kWavesPerBlock), 0, ctx->stream, bytes, total,
-                       rv, w, (int)bound, d_status);
+    hipLaunchKernelGGL(encoded_check, chunk_grid(total, ctx->grid_check), dim3(64 * kWavesPerBlock), 0, ctx->stream, bytes, total, rv, w,
+                       (int)bound, d_status);
     return fz_check_hip(hipGetLastError(), "encoded_check launch");
 }
 

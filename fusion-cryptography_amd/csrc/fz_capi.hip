@@ -387,21 +387,27 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
 }
 
+// a bound B of some kind of record, `what` for the message: B in [1, (q-1)/2] -> *w = bit_length(2 B), the kind's field width
+static int records_bound(const fz_ctx *ctx, int64_t bound, const char *what, int *w) {
+    FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "%s %lld outside [1, (q-1)/2]", what, (long long)bound);
+    int b = 0;
+    while ((2 * bound) >> b) ++b;
+    *w = b;
+    return FZ_OK;
+}
+
 // compact byte encoding: the checks of all seven entries, in the order that decides the return code when more than one thing is
 // wrong: context, rows and bound; n == 0 is FZ_OK from here on; the entry's pointers (`ptrs_wrong`: what is wrong with them, NULL
 // when nothing is -- which pointers an entry takes and how they must be aligned is its own business); degree; size.
-// -> *w = bit_length(2 * bound).  Conditions of an entry that hold whatever n is come before this call, its own limits after it.
+// -> *w = the field width (records_bound).  Conditions of an entry that hold whatever n is come before this call, its own limits after it.
 static int records_args(fz_ctx *ctx, size_t n, int rows, int64_t bound, const char *ptrs_wrong, int *w) {
     FZ_REQUIRE(ctx && rows >= 1, "bad argument");
-    FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "bound %lld outside [1, (q-1)/2]", (long long)bound);
+    FZ_TRY(records_bound(ctx, bound, "bound", w));
     if (n == 0) return FZ_OK;
     FZ_REQUIRE(!ptrs_wrong, "%s", ptrs_wrong);
     if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
     FZ_REQUIRE((uint64_t)rows * (uint64_t)ctx->degree <= 0x7fffffffull && n <= ((size_t)-1 >> 3) / ((size_t)rows * ctx->degree),
                "%zu records of %d rows are too many", n, rows);
-    int b = 0;
-    while ((2 * bound) >> b) ++b;
-    *w = b;
     return FZ_OK;
 }
 
@@ -458,10 +464,9 @@ int fz_sign_records_async(fz_ctx *ctx, const uint8_t *d_key_bytes, int64_t key_b
     const char *ptrs_wrong = records_ptrs(d_key_bytes, d_bytes, d_status);
     if (!ptrs_wrong) ptrs_wrong = records_ptrs(d_c_hat, d_c_hat, d_c_hat);
     FZ_REQUIRE(ctx && l >= 1, "bad argument");
-    FZ_REQUIRE(key_bound >= 1 && key_bound <= ((int64_t)ctx->q - 1) / 2, "key bound %lld outside [1, (q-1)/2]", (long long)key_bound);
+    FZ_TRY(records_bound(ctx, key_bound, "key bound", &wk));
     FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
     if (N == 0) return FZ_OK;
-    while ((2 * key_bound) >> wk) ++wk;
     FZ_DEV(ctx);
     return fz_launch_sign_records(ctx, d_key_bytes, wk, key_bound, d_c_hat, N, l, w, bound, d_bytes, d_status);
 }

@@ -280,6 +280,18 @@ int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_
 // the follow-up of every launch that leaves records and status words: record i of `dst` (rec_bytes each, a multiple of 8) is
 // zeroed where d_status[i] != 0
 int fz_launch_records_zero(fz_ctx *ctx, const int *d_status, size_t n, void *dst, size_t rec_bytes);
+// the launch sequence of every pass that leaves records and status words: d_status [n] cleared, launch() (the caller's dispatch on
+// degree and multiply form; FZ_OK when it launched), the launch error named `what`, then the zeroing above.  Asynchronous and
+// allocation-free: a graph capture records all three.
+template <class F>
+int fz_records_pass(fz_ctx *ctx, int *d_status, size_t n, const char *what, F &&launch, void *dst, size_t rec_bytes) {
+    int rc = fz_check_hip(hipMemsetAsync(d_status, 0, n * sizeof(int), ctx->stream), "records status clear");
+    if (rc != FZ_OK) return rc;
+    rc = launch();
+    if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), what);
+    if (rc != FZ_OK) return rc;
+    return fz_launch_records_zero(ctx, d_status, n, dst, rec_bytes);
+}
 
 // signing straight to the bytes (fz_sign_encoded.hip; degree 64 / 256): record i of d_bytes = the encoding of
 // cent(cent(L_i (.) c_i) + R_i) from sk_hat [n][2][l][degree] and c_hat [n][degree], any int32; d_status [n] cleared, then 0 or

@@ -74,6 +74,19 @@ __device__ __forceinline__ void chunk_to_lds(int32_t *stage, int lane, const Chu
     *reinterpret_cast<int4 *>(stage + pad4(768 + 4 * lane)) = c.v3;
 }
 
+// a lane's 16 consecutive values of the image as doubles (LANDED: of the unpadded chunk as chunk_load_lds leaves it, below)
+template <bool LANDED = false>
+__device__ __forceinline__ void image_to_doubles(const int32_t *img, int lane, double (&a)[16]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int4 t = *reinterpret_cast<const int4 *>(img + (LANDED ? 16 * lane + 4 * k : pad4(16 * lane + 4 * k)));
+        a[4 * k + 0] = (double)t.x;
+        a[4 * k + 1] = (double)t.y;
+        a[4 * k + 2] = (double)t.z;
+        a[4 * k + 3] = (double)t.w;
+    }
+}
+
 // Wave-local synchronisation.  Every LDS exchange in these kernels is between lanes of ONE wave
 // (each wave owns a private staging region), and a wave's DS instructions execute in order, so no
 // s_barrier is needed: the release/acquire pair makes the compiler wait for the outstanding LDS
@@ -547,14 +560,7 @@ __device__ __forceinline__ void inv16_run(const int32_t *in, int32_t *out, size_
         if constexpr (!landed) chunk_to_lds(stage, lane, chunk_load(in, task, total, lane));
         wave_sync();
         double a[16];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int4 t = *reinterpret_cast<const int4 *>(landed ? land + 16 * lane + 4 * k : stage + pad4(16 * lane + 4 * k));
-            a[4 * k + 0] = (double)t.x;
-            a[4 * k + 1] = (double)t.y;
-            a[4 * k + 2] = (double)t.z;
-            a[4 * k + 3] = (double)t.w;
-        }
+        image_to_doubles<landed>(landed ? land : stage, lane, a);
         wave_sync();
 
         inv16_passes<LOGD, FAST, true>(a, row, r, s_tw, twA, m, [&]() __attribute__((always_inline)) {

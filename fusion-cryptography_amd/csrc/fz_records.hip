@@ -12,48 +12,33 @@ template <int LOGD, bool FAST, bool COEF>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int32_t *in, uint8_t *out, size_t total, unsigned rec_values,
                                                                       int w, int bound, int *status, const double2 *__restrict__ itwB,
                                                                       const FzTwA *tab, FzMod m) {
-    constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
+    constexpr int L = Geom<LOGD>::L;
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int p = lane / L, r = lane % L;
-    const size_t tasks = (total + kChunk - 1) / kChunk;
-    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
-    const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
+    const int lane = threadIdx.x & 63, p = lane / L, r = lane % L;
+    const ChunkTasks T(total);
     Chunk raw0 = {};
-    if (first < tasks) raw0 = chunk_load(in, first, total, lane);      // before the table: see fwd16_run
+    if (T.first < T.tasks) raw0 = chunk_load(in, T.first, total, lane);      // before the table: see fwd16_run
     const double2 *s_tw = nullptr;
     if constexpr (COEF) s_tw = twiddles_to_lds<LOGD>(lds, itwB);
-    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
-    if (first >= tasks) return;
+    const WaveLds W = wave_lds<LOGD>(lds, T.wave, p);
+    if (T.first >= T.tasks) return;
     chunk_to_lds(W.stage, lane, raw0);
-    RecWalk walk(first, stride, rec_values, lane);
-    unsigned two_b = 2u * (unsigned)bound, wmask = (unsigned)((1ull << w) - 1), bnd = (unsigned)bound;
-    asm volatile("" : "+v"(two_b), "+v"(wmask), "+v"(bnd));       // VALU operands only (see RecWalk)
+    RecWalk walk(T.first, T.stride, rec_values, lane);
+    const FieldBounds B(w, bound);
 
     auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {       // pipeline and peeling: see fwd16_run
         constexpr bool more = decltype(more_tag)::value;
         Chunk raw = {};
-        if (more) raw = chunk_load(in, task + stride, total, lane);
+        if (more) raw = chunk_load(in, task + T.stride, total, lane);
         int wl = w;
         asm volatile("" : "+s"(wl));                      // what depends on w alone (the bit offsets of the packing, the stream's
         const size_t total_bytes = total / 8 * (size_t)wl;      // length) is recomputed per chunk, not held across the loop
         wave_sync();
         if constexpr (COEF) {
             double a[16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int4 t = *reinterpret_cast<const int4 *>(W.stage + pad4(16 * lane + 4 * k));
-                a[4 * k + 0] = (double)t.x;
-                a[4 * k + 1] = (double)t.y;
-                a[4 * k + 2] = (double)t.z;
-                a[4 * k + 3] = (double)t.w;
-            }
+            image_to_doubles(W.stage, lane, a);
             wave_sync();
-            TabPtr t = (TabPtr)tab;
-            asm volatile("" : "+s"(t));
-            inv16_passes<LOGD, FAST>(a, W.row, r, s_tw, t[0], m);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) W.stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
+            inv16_to_image<LOGD, FAST>(a, W, p, r, s_tw, (TabPtr)tab, m);
             wave_sync();
         }
         // the lane's 16 consecutive values: centred (the transform's outputs already are), range-checked, packed
@@ -66,25 +51,21 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_encode(const int3
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const long long z = COEF ? (long long)v[i] : (long long)fz_cent((double)v[i], m);
-                const unsigned long long s = (unsigned long long)(z + (long long)bnd);
-                hi |= (uint32_t)(s >> 32);
-                mx = max(mx, (uint32_t)s);
-                u[4 * k + i] = (uint32_t)s & wmask;       // a refused field stays inside its own w bits
+                u[4 * k + i] = range_field(z, B, hi, mx);
             }
         }
-        const bool bad = hi != 0 || mx > two_b;
+        const bool bad = hi != 0 || mx > B.two_b;
+        // (fields_pack and the read-back stay written out: inside a helper the packing comes out longer, docs/HISTORY.md section V)
         fields_pack(reinterpret_cast<uint16_t *>(W.pk) + lane * wl, u, wl);
         wave_sync();
         const Packed o = packed_from_lds(W.pk, wl, lane);
         wave_sync();
         if (more) chunk_to_lds(W.stage, lane, raw);       // waits for the prefetched loads (no store is younger)
-        packed_store(out, task, total_bytes, wl, lane, o);
-        const bool valid = task * kChunk + 16 * lane < total;
-        records_flag(status, walk.rec, bad && valid, FZ_VERDICT_NORM, lane);
+        store_and_flag(out, task, total, total_bytes, wl, lane, o, status, walk.rec, bad, FZ_VERDICT_NORM);
         walk.step();
     };
-    size_t task = first;
-    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
+    size_t task = T.first;
+    for (; task + T.stride < T.tasks; task += T.stride) iteration(task, std::true_type());
     iteration(task, std::false_type());
 }
 
@@ -99,8 +80,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void records_decode(const uint
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int p = lane / L, r = lane % L;
     const size_t tasks = (total + kChunk - 1) / kChunk;
-    const size_t total_bytes = total / 8 * (size_t)w;
-    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
+    const size_t total_bytes = total / 8 * (size_t)w;      // (ChunkTasks' text, kept here: with the length in front of it or behind
+    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;      // it this kernel's prologue changes, docs/HISTORY.md section V)
     const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
     Packed raw0 = {};
     if (first < tasks) raw0 = packed_load(in, first, total_bytes, w, lane);
@@ -173,17 +154,15 @@ __global__ __launch_bounds__(256) void records_zero_failed(const int *status, si
 
 }  // namespace
 
-// compact byte encoding (fz_encode_records_async / fz_decode_records_async): d_status cleared, the records kernel over the batch,
-// then the zeroing of failed records.  Asynchronous and allocation-free: a graph capture records all three.  Verification keys (no
-// transform) take one instantiation.  The grid is capped at the kernel's OWN resident grid (fz_records_query_grid), as launch16f caps
-// the transforms at theirs: the FAST encode holds more registers than ntt_inv16 (3 workgroups per CU against 4), and a grid sized
-// for the transform would leave a quarter of its workgroups for a second round of the grid-stride walk.
+// compact byte encoding (fz_encode_records_async / fz_decode_records_async): the records kernel over the batch as a
+// fz_records_pass.  Verification keys (no transform) take one instantiation.  The grid is capped at the kernel's OWN resident grid
+// (fz_records_query_grid), as launch16f caps the transforms at theirs: the FAST encode holds more registers than ntt_inv16 (3
+// workgroups per CU against 4), and a grid sized for the transform would leave a quarter of its workgroups for a second round of
+// the grid-stride walk.
 template <int LOGD, bool FAST, bool COEF>
 static void launch_records_k(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t total, unsigned rv, int w, int bound,
                              int *d_status) {
-    const size_t tasks = (total + kChunk - 1) / kChunk, blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
-    const size_t cap = (size_t)ctx->grid_rec[(decode ? 1 : 0) + (COEF ? 0 : 2)];
-    const dim3 grid((unsigned)(blocks < cap ? blocks : cap)), block(64 * kWavesPerBlock);
+    const dim3 grid = chunk_grid(total, ctx->grid_rec[(decode ? 1 : 0) + (COEF ? 0 : 2)]), block(64 * kWavesPerBlock);
     if (decode)
         hipLaunchKernelGGL((records_decode<LOGD, FAST, COEF>), grid, block, 0, ctx->stream, (const uint8_t *)src, (int32_t *)dst, total, rv,
                            w, bound, d_status, (const double2 *)ctx->d_twB, (const FzTwA *)ctx->d_twAB, ctx->mod);
@@ -210,18 +189,18 @@ int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size
                       int *d_status) {
     const unsigned rv = (unsigned)rows * (unsigned)ctx->degree;
     const size_t total = n * rv;
-    int rc = fz_check_hip(hipMemsetAsync(d_status, 0, n * sizeof(int), ctx->stream), "records status clear");
-    if (rc != FZ_OK) return rc;
     const int b = (int)bound;
-    if (!coef) launch_records_k<8, true, false>(ctx, decode, src, dst, total, rv, w, b, d_status);
-    else
-        rc = fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
-            launch_records_k<logd(), fast(), true>(ctx, decode, src, dst, total, rv, w, b, d_status);
-            return FZ_OK;
-        });
-    if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "records launch");
-    if (rc != FZ_OK) return rc;
-    return fz_launch_records_zero(ctx, d_status, n, dst, decode ? (size_t)rv * sizeof(int32_t) : fz_record_bytes(ctx->degree, rows, w));
+    const auto launch = [&]() {
+        if (coef)
+            return fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
+                launch_records_k<logd(), fast(), true>(ctx, decode, src, dst, total, rv, w, b, d_status);
+                return FZ_OK;
+            });
+        launch_records_k<8, true, false>(ctx, decode, src, dst, total, rv, w, b, d_status);
+        return (int)FZ_OK;
+    };
+    return fz_records_pass(ctx, d_status, n, "records launch", launch, dst,
+                           decode ? (size_t)rv * sizeof(int32_t) : fz_record_bytes(ctx->degree, rows, w));
 }
 
 int fz_launch_records_zero(fz_ctx *ctx, const int *d_status, size_t n, void *dst, size_t rec_bytes) {

@@ -3,9 +3,11 @@
 // and the aggregation straight from the bytes, of one committee and of many; fz_verify_encoded.hip:
 // the verification straight from the bytes; fz_sign_encoded.hip: signing straight to the bytes; fz_sign_records.hip: signing
 // straight from the key's bytes to the signature's): the packed chunk of the chunk
-// walk with its loads and stores, the field packing and unpacking, the steps from the packed chunk to the transform's outputs and
-// their sums, the per-record status flag and the record walk.  No kernels and no host code here; everything is private to the
-// unit that includes it.
+// walk with its loads and stores, the field packing and unpacking, the consumers' steps from the packed chunk to the transform's
+// outputs and their sums, the per-record status flag, the record walk, the chunk walk's opening, and the producers' steps from
+// the int32 image to the stored chunk (the range check's operands and its per-value step, the inverse transform centred into the
+// image, store and flag).  No kernels here, and of host code only chunk_grid, the launch grid of the chunk walk; everything is
+// private to the unit that includes it.
 #ifndef FZ_RECORDS_DEV_H
 #define FZ_RECORDS_DEV_H
 
@@ -216,13 +218,16 @@ struct WaveLds {
     double *region;      // the wave's transpose region
     int32_t *stage;      // the int32 image at its start
     uint8_t *pk;         // the packed chunk behind the image
+    int32_t *land;       // the same place as the landing area of a chunk requested straight into LDS
     double *row;         // the transpose buffer of the lane's polynomial p
 };
 template <int LOGD>
 __device__ __forceinline__ WaveLds wave_lds(double *lds, int wave, int p) {
     using G = Geom<LOGD>;
+    static_assert(landing_fits<LOGD>() && kLandOff * 4 == kPackOff, "the landing area is the packed chunk's place");
     double *region = lds + wave * G::PPW * G::PS;
-    return {region, reinterpret_cast<int32_t *>(region), reinterpret_cast<uint8_t *>(region) + kPackOff, region + p * G::PS};
+    int32_t *stage = reinterpret_cast<int32_t *>(region);
+    return {region, stage, reinterpret_cast<uint8_t *>(region) + kPackOff, stage + kLandOff, region + p * G::PS};
 }
 
 // Per-record status: every (wave, record) with a failing lane sets its record's word with ONE atomic (at most 16 records meet
@@ -239,8 +244,22 @@ __device__ __forceinline__ void records_flag(int *status, size_t rec, bool bad, 
     }
 }
 
+// (record, offset inside it) moved on by srec records and soff < rv values: an add, a compare and a select.  S is the caller's
+// type of srec (size_t or unsigned): widened here, the sum srec + c comes out as other instructions in sign_encode.
+template <class S>
+__device__ __forceinline__ void rec_advance(size_t &rec, unsigned &off, S srec, unsigned soff, unsigned rv) {
+    off += soff;                                          // < 2 * rv: no overflow, rv < 2^31
+    const unsigned c = off >= rv ? 1u : 0u;
+    rec += srec + c;
+    off -= c * rv;
+}
+
 // the record of a lane's first value, walked along the wave's chunks: the divisions run once per wave (constructor), a step is
-// an add, a compare and a select (per lane: the uniform state would compete with the transform's scalar operands)
+// rec_advance (per lane: the uniform state would compete with the transform's scalar operands)
+struct RecPos {
+    size_t rec;
+    unsigned off;
+};
 struct RecWalk {
     size_t rec, srec;
     unsigned off, soff, rv;
@@ -252,13 +271,76 @@ struct RecWalk {
         soff = (unsigned)(s - srec * rv);
         asm volatile("" : "+v"(srec), "+v"(soff), "+v"(rv));      // uniform, but VALU operands only: out of the scalar file
     }
-    __device__ __forceinline__ void step() {
-        off += soff;                                      // < 2 * rv: no overflow, rv < 2^31
-        const unsigned c = off >= rv ? 1u : 0u;
-        rec += srec + c;
-        off -= c * rv;
+    __device__ __forceinline__ void step() { rec_advance(rec, off, srec, soff, rv); }
+    // where the walk stands after its next step, without stepping it
+    __device__ __forceinline__ RecPos next() const {
+        RecPos n = {rec, off};
+        rec_advance(n.rec, n.off, srec, soff, rv);
+        return n;
     }
 };
+
+// The chunk walk of a kernel whose wave-task is one chunk of a stream of `total` values: the wave's tasks are first, first +
+// stride, .. below `tasks`.  The kernel takes its lane first (held here, sign_encode's prologue comes out in another order) and
+// writes the peeled loop over the tasks itself, as fwd16_run explains it: run by a function here, the loop and the iteration no
+// longer share their task + stride (docs/HISTORY.md section V).
+struct ChunkTasks {
+    int wave;                                             // uniform: readfirstlane says so (scalar address arithmetic)
+    size_t tasks, first, stride;
+    __device__ __forceinline__ explicit ChunkTasks(size_t total)
+        : wave(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)), tasks((total + kChunk - 1) / kChunk),
+          first((size_t)blockIdx.x * kWavesPerBlock + wave), stride((size_t)gridDim.x * kWavesPerBlock) {}
+};
+// its grid (host): a workgroup per kWavesPerBlock tasks, at most `cap` of them (the kernel's resident grid)
+inline dim3 chunk_grid(size_t total, int cap) {
+    const size_t tasks = (total + kChunk - 1) / kChunk, blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
+    return dim3((unsigned)(blocks < (size_t)cap ? blocks : (size_t)cap));
+}
+
+// The steps every producer of the bytes takes once its chunk's int32 image stands in the wave's region.  Each has the form that
+// leaves its callers' code as it was with the text in place, or the callers say why not (docs/HISTORY.md section V).  Three
+// steps stay with the kernels, each a few lines: the field width pinned per chunk with the stream's length, `bad` from the two
+// halves, and fields_pack with the read-back of the packed chunk -- every form of a helper for them changes the callers' code.
+
+// the operands of the range check: uniform, but VALU operands only (see RecWalk)
+struct FieldBounds {
+    unsigned two_b, wmask, bnd;
+    __device__ __forceinline__ FieldBounds(int w, int bound)
+        : two_b(2u * (unsigned)bound), wmask((unsigned)((1ull << w) - 1)), bnd((unsigned)bound) {
+        asm volatile("" : "+v"(two_b), "+v"(wmask), "+v"(bnd));
+    }
+};
+
+// a centred value z -> its field u = z + B, range-checked in the two-halves form: |z + B| < 2^32, the high word is all ones
+// exactly when z < -B and the low word exceeds 2B exactly when z > B, so the lane's values are out of range exactly when
+// hi != 0 || mx > two_b after the last of them.  A refused field stays inside its own w bits.
+__device__ __forceinline__ uint32_t range_field(const long long &z, const FieldBounds &b, uint32_t &hi, uint32_t &mx) {
+    const unsigned long long s = (unsigned long long)(z + (long long)b.bnd);
+    hi |= (uint32_t)(s >> 32);
+    mx = max(mx, (uint32_t)s);
+    return (uint32_t)s & b.wmask;
+}
+
+// the inverse passes on a[k] = value 16 * lane + k of the image (image_to_doubles; the caller's wave_sync lies behind the read)
+// and their outputs, element r + L * k of polynomial p, centred into the image.  The wave-uniform table is taken from constant
+// memory, its pointer pinned (TabPtr); `transposed` is inv16_passes' hook.
+template <int LOGD, bool FAST, class HOOK = NoHook>
+__device__ __forceinline__ void inv16_to_image(double (&a)[16], const WaveLds &W, int p, int r, const double2 *s_tw, TabPtr t,
+                                               const FzMod &m, const HOOK &transposed = HOOK()) {
+    constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
+    asm volatile("" : "+s"(t));
+    inv16_passes<LOGD, FAST>(a, W.row, r, s_tw, t[0], m, transposed);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) W.stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
+}
+
+// the packed chunk to the stream, and `code` to the status word of the lane's record where `bad` (lanes with values only)
+__device__ __forceinline__ void store_and_flag(uint8_t *out, size_t task, size_t total, size_t total_bytes, int w, int lane,
+                                               const Packed &o, int *status, size_t rec, bool bad, int code) {
+    packed_store(out, task, total_bytes, w, lane, o);
+    const bool valid = task * kChunk + 16 * lane < total;
+    records_flag(status, rec, bad && valid, code, lane);
+}
 
 }  // namespace
 

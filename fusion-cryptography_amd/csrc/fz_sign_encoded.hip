@@ -22,12 +22,7 @@ struct PieceWalk {
         poff = 256u % rec_values;
         asm volatile("" : "+v"(prec), "+v"(poff));       // uniform, but VALU operands only (see RecWalk)
     }
-    __device__ __forceinline__ void step(const RecWalk &w) {
-        off += w.soff;
-        const unsigned c = off >= w.rv ? 1u : 0u;
-        rec += w.srec + c;
-        off -= c * w.rv;
-    }
+    __device__ __forceinline__ void step(const RecWalk &w) { rec_advance(rec, off, w.srec, w.soff, w.rv); }
     // f(j, record, offset) for the lane's pieces j = 0 .. 3 of chunk `task`, the chunk the walk stands at; a piece past the end of
     // the batch (a ragged last chunk's) is given the batch's first values instead: read, transformed in polynomials of their own
     // and never stored
@@ -40,10 +35,7 @@ struct PieceWalk {
         for (int j = 0; j < 4; ++j) {
             const bool in = e + 256 * j < total;
             f(j, in ? pr : (size_t)0, in ? po : 0u);
-            po += poff;
-            const unsigned c = po >= rv ? 1u : 0u;
-            pr += prec + c;
-            po -= c * rv;
+            rec_advance(pr, po, prec, poff, rv);
         }
     }
 };
@@ -137,32 +129,26 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_encode(const int32_t
                                                                    unsigned rec_values, int w, int bound, int *status,
                                                                    const double2 *__restrict__ itwB, const FzTwA *tab, FzMod m) {
     constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
-    static_assert(landing_fits<LOGD>() && kLandOff * 4 == kPackOff, "the landing area is the packed chunk's place");
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int p = lane / L, r = lane % L;
-    const size_t tasks = (total + kChunk - 1) / kChunk;
-    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
-    const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
+    const int lane = threadIdx.x & 63, p = lane / L, r = lane % L;
+    const ChunkTasks T(total);
     // the three pointers only the lanes' own address arithmetic uses: VALU operands, out of the scalar file (see RecWalk) -- with
     // them there the FAST forms spill scalar registers beside the strided pass's table
     asm volatile("" : "+v"(sk_hat), "+v"(c_hat), "+v"(status));
-    RecWalk walk(first, stride, rec_values, lane);        // the addresses need the walks: before the first loads here
-    PieceWalk pw(first, rec_values, lane);
+    RecWalk walk(T.first, T.stride, rec_values, lane);    // the addresses need the walks: before the first loads here
+    PieceWalk pw(T.first, rec_values, lane);
     KeyChunk raw0 = {};
-    if (first < tasks) raw0 = key_load(sk_hat, pw, first, total, walk.rv, lane);      // before the table: see fwd16_run
+    if (T.first < T.tasks) raw0 = key_load(sk_hat, pw, T.first, total, walk.rv, lane);      // before the table: see fwd16_run
     const double2 *s_tw = twiddles_to_lds<LOGD>(lds, itwB);
-    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
-    if (first >= tasks) return;
-    int32_t *land = W.stage + kLandOff;
+    const WaveLds W = wave_lds<LOGD>(lds, T.wave, p);
+    if (T.first >= T.tasks) return;
     {
         int4 c[4];
-        chal_load<D>(c_hat, pw, first, total, walk.rv, lane, c);
+        chal_load<D>(c_hat, pw, T.first, total, walk.rv, lane, c);
         sign_image(W.stage, lane, raw0, c, m);
     }
     pw.step(walk);                                        // from here on the walk stands at the chunk that is requested next
-    unsigned two_b = 2u * (unsigned)bound, wmask = (unsigned)((1ull << w) - 1), bnd = (unsigned)bound;
-    asm volatile("" : "+v"(two_b), "+v"(wmask), "+v"(bnd));       // VALU operands only (see RecWalk)
+    const FieldBounds B(w, bound);
 
     auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {
         constexpr bool more = decltype(more_tag)::value;
@@ -173,27 +159,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_encode(const int32_t
         wave_sync();
         {
             double a[16];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int4 t = *reinterpret_cast<const int4 *>(W.stage + pad4(16 * lane + 4 * k));
-                a[4 * k + 0] = (double)t.x;
-                a[4 * k + 1] = (double)t.y;
-                a[4 * k + 2] = (double)t.z;
-                a[4 * k + 3] = (double)t.w;
-            }
+            image_to_doubles(W.stage, lane, a);
             wave_sync();
-            TabPtr t = (TabPtr)tab;
-            asm volatile("" : "+s"(t));
-            inv16_passes<LOGD, FAST>(a, W.row, r, s_tw, t[0], m, [&]() __attribute__((always_inline)) {
-                if constexpr (more) key_request(sk_hat, pw, task + stride, total, walk.rv, lane, land, raw);
+            inv16_to_image<LOGD, FAST>(a, W, p, r, s_tw, (TabPtr)tab, m, [&]() __attribute__((always_inline)) {
+                if constexpr (more) key_request(sk_hat, pw, task + T.stride, total, walk.rv, lane, W.land, raw);
             });
-#pragma unroll
-            for (int k = 0; k < 16; ++k) W.stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
             if constexpr (more) wave_sync_inflight();     // not a wait for the pieces in flight
             else wave_sync();
         }
-        // the lane's 16 consecutive values, centred by the transform: range-checked in the two-halves form (|z + B| < 2^32: the
-        // high word is all ones exactly when z < -B, the low word exceeds 2B exactly when z > B), packed
+        // the lane's 16 consecutive values, centred by the transform: range-checked, packed
         uint32_t u[16], hi = 0, mx = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -201,19 +175,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_encode(const int32_t
             const int v[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const unsigned long long s = (unsigned long long)((long long)v[i] + (long long)bnd);
-                hi |= (uint32_t)(s >> 32);
-                mx = max(mx, (uint32_t)s);
-                u[4 * k + i] = (uint32_t)s & wmask;       // a refused field stays inside its own w bits
+                const long long z = v[i];
+                u[4 * k + i] = range_field(z, B, hi, mx);
             }
         }
-        const bool bad = hi != 0 || mx > two_b;
+        const bool bad = hi != 0 || mx > B.two_b;
         int4 c[4];
         if constexpr (more) {
-            key_landed(land, lane, raw);
-            chal_load<D>(c_hat, pw, task + stride, total, walk.rv, lane, c);
+            key_landed(W.land, lane, raw);
+            chal_load<D>(c_hat, pw, task + T.stride, total, walk.rv, lane, c);
             wave_sync();                                  // the landing area has been read: it is the packed chunk's now
         }
+        // (fields_pack and the read-back stay written out: inside a helper the packing comes out longer, docs/HISTORY.md section V)
         fields_pack(reinterpret_cast<uint16_t *>(W.pk) + lane * wl, u, wl);
         wave_sync();
         const Packed o = packed_from_lds(W.pk, wl, lane);
@@ -222,22 +195,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_encode(const int32_t
             sign_image(W.stage, lane, raw, c, m);
             pw.step(walk);
         }
-        packed_store(out, task, total_bytes, wl, lane, o);
-        const bool valid = task * kChunk + 16 * lane < total;
-        records_flag(status, walk.rec, bad && valid, FZ_VERDICT_NORM, lane);
+        store_and_flag(out, task, total, total_bytes, wl, lane, o, status, walk.rec, bad, FZ_VERDICT_NORM);
         walk.step();
     };
-    size_t task = first;
-    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
+    size_t task = T.first;
+    for (; task + T.stride < T.tasks; task += T.stride) iteration(task, std::true_type());
     iteration(task, std::false_type());
 }
 
 template <int LOGD, bool FAST>
 void launch_sign_encode(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat, uint8_t *bytes, size_t total, unsigned rv, int w,
                         int bound, int *d_status) {
-    const size_t tasks = (total + kChunk - 1) / kChunk, blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
-    const size_t cap = (size_t)ctx->grid_signenc;
-    hipLaunchKernelGGL((sign_encode<LOGD, FAST>), dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(64 * kWavesPerBlock), 0, ctx->stream,
+    hipLaunchKernelGGL((sign_encode<LOGD, FAST>), chunk_grid(total, ctx->grid_signenc), dim3(64 * kWavesPerBlock), 0, ctx->stream,
                        sk_hat, c_hat, bytes, total, rv, w, bound, d_status, (const double2 *)ctx->d_itwB, (const FzTwA *)ctx->d_twAB + 1,
                        ctx->mod);
 }
@@ -255,19 +224,16 @@ int fz_sign_encoded_query_grid(fz_ctx *ctx) {
     return rc != FZ_OK ? rc : fz_aggregate_many_encoded_query_grid(ctx);
 }
 
-// fz_sign_encoded_async: d_status cleared, the fused pass over the batch, then the zeroing of refused records (fz_records.hip's).
-// Asynchronous and allocation-free: a graph capture records all three.
+// fz_sign_encoded_async: the fused pass over the batch as a fz_records_pass
 int fz_launch_sign_encoded(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat, size_t n, int l, int w, int64_t bound,
                            uint8_t *d_bytes, int *d_status) {
     const unsigned rv = (unsigned)l * (unsigned)ctx->degree;
     const size_t total = n * rv;
-    int rc = fz_check_hip(hipMemsetAsync(d_status, 0, n * sizeof(int), ctx->stream), "records status clear");
-    if (rc != FZ_OK) return rc;
-    rc = fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
-        launch_sign_encode<logd(), fast()>(ctx, sk_hat, c_hat, d_bytes, total, rv, w, (int)bound, d_status);
-        return FZ_OK;
-    });
-    if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "sign_encode launch");
-    if (rc != FZ_OK) return rc;
-    return fz_launch_records_zero(ctx, d_status, n, d_bytes, fz_record_bytes(ctx->degree, l, w));
+    const auto launch = [&]() {
+        return fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
+            launch_sign_encode<logd(), fast()>(ctx, sk_hat, c_hat, d_bytes, total, rv, w, (int)bound, d_status);
+            return FZ_OK;
+        });
+    };
+    return fz_records_pass(ctx, d_status, n, "sign_encode launch", launch, d_bytes, fz_record_bytes(ctx->degree, l, w));
 }

@@ -106,37 +106,32 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_records(const uint8_
                                                                     int *status, const double2 *__restrict__ twB,
                                                                     const double2 *__restrict__ itwB, const FzTwA *tabs, FzMod m) {
     constexpr int D = Geom<LOGD>::D, L = Geom<LOGD>::L;
-    static_assert(landing_fits<LOGD>() && kLandOff * 4 == kPackOff, "the landing area is the packed chunk's place");
     __shared__ __attribute__((aligned(16))) double lds[lds16_doubles<LOGD>()];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int p = lane / L, r = lane % L;
-    const size_t tasks = (total + kChunk - 1) / kChunk;
-    const size_t first = (size_t)blockIdx.x * kWavesPerBlock + wave;
-    const size_t stride = (size_t)gridDim.x * kWavesPerBlock;
+    const int lane = threadIdx.x & 63, p = lane / L, r = lane % L;
+    const ChunkTasks T(total);
     // what only the lanes' own address arithmetic uses: VALU operands, out of the scalar file (see RecWalk) -- and the walk's
     // own counters with them: two transforms' tables pass through the scalar file per chunk, and what is live across both is
     // saved around each
     asm volatile("" : "+v"(key), "+v"(c_hat), "+v"(status), "+v"(twB), "+v"(out), "+v"(total));
-    RecWalk walk(first, stride, rec_values, lane);
-    const WaveLds W = wave_lds<LOGD>(lds, wave, p);
-    int32_t *land = W.stage + kLandOff;
+    RecWalk walk(T.first, T.stride, rec_values, lane);
+    const WaveLds W = wave_lds<LOGD>(lds, T.wave, p);
     unsigned kb = (unsigned)key_bound, two_kb = 2u * (unsigned)key_bound;
     asm volatile("" : "+v"(kb), "+v"(two_kb));
     // the lane's fields of a chunk it has no value in (a ragged last chunk's) are the batch's first: read, transformed in
     // polynomials of their own, never stored and never flagged
     unsigned h0 = 0;
-    if (first < tasks) {                                  // before the table: see fwd16_run
-        const bool in = first * kChunk + 16 * lane < total;
+    if (T.first < T.tasks) {                              // before the table: see fwd16_run
+        const bool in = T.first * kChunk + 16 * lane < total;
         const KeyAddr ka = key_addr(key, in ? walk.rec : (size_t)0, in ? walk.off : 0u, walk.rv, wk);
         h0 = ka.h;
-        key_request_lds(ka, (wk + 1) >> 1, land);
+        key_request_lds(ka, (wk + 1) >> 1, W.land);
     }
     const double2 *s_tw = twiddles_to_lds<LOGD>(lds, itwB);
-    if (first >= tasks) return;
+    if (T.first >= T.tasks) return;
     // the left fields -> the image (chunk_to_lds' layout), -> is one of them above 2 kb?
     auto left_image = [&](unsigned h, int wkl) __attribute__((always_inline)) {
         uint32_t u[16];
-        const uint32_t mx = key_unpack(land, lane, h, wkl, u);
+        const uint32_t mx = key_unpack(W.land, lane, h, wkl, u);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             int4 t;
@@ -150,8 +145,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_records(const uint8_
     };
     chunk_landed<0>();
     uint32_t key_mx = left_image(h0, wk);                 // the largest key field of the lane's 16 values: a register, not a lane mask
-    unsigned two_b = 2u * (unsigned)bound, wmask = (unsigned)((1ull << w) - 1), bnd = (unsigned)bound;
-    asm volatile("" : "+v"(two_b), "+v"(wmask), "+v"(bnd));       // VALU operands only (see RecWalk)
+    const FieldBounds B(w, bound);
 
     auto iteration = [&](const size_t task, auto more_tag) __attribute__((always_inline)) {
         constexpr bool more = decltype(more_tag)::value;
@@ -187,27 +181,19 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_records(const uint8_
                 for (int k = 0; k < 16; ++k) a[k] = fz_cent(fz_mulmod(a[k], (double)x[k], m), m);
             }
             wave_sync();
-            TabPtr t = (TabPtr)tabs + 1;
-            asm volatile("" : "+s"(t));
-            inv16_passes<LOGD, FAST>(a, W.row, r, s_tw, t[0], m, [&]() __attribute__((always_inline)) {
+            inv16_to_image<LOGD, FAST>(a, W, p, r, s_tw, (TabPtr)tabs + 1, m, [&]() __attribute__((always_inline)) {
                 const bool valid = is_valid();
                 const KeyAddr ka = key_addr(key, valid ? walk.rec : (size_t)0, valid ? walk.off : 0u, walk.rv, wkl);
                 hc = ka.h;
                 key_request(ka, key_half_bytes(walk.rv, wkl), ndw, right);
                 if constexpr (more) {
-                    // the chunk the walk reaches next, without stepping it
-                    unsigned noff = walk.off + walk.soff;
-                    const unsigned cy = noff >= walk.rv ? 1u : 0u;
-                    const size_t nrec = walk.rec + walk.srec + cy;
-                    noff -= cy * walk.rv;
-                    const bool in = (task + stride) * kChunk + 16 * lane < total;
-                    const KeyAddr kn = key_addr(key, in ? nrec : (size_t)0, in ? noff : 0u, walk.rv, wkl);
+                    const RecPos n = walk.next();
+                    const bool in = (task + T.stride) * kChunk + 16 * lane < total;
+                    const KeyAddr kn = key_addr(key, in ? n.rec : (size_t)0, in ? n.off : 0u, walk.rv, wkl);
                     hn = kn.h;
-                    key_request_lds(kn, ndw, land);
+                    key_request_lds(kn, ndw, W.land);
                 }
             });
-#pragma unroll
-            for (int k = 0; k < 16; ++k) W.stage[pad4(p * D + r + L * k)] = (int)fz_cent(a[k], m);
             if constexpr (more) wave_sync_inflight();     // not a wait for the words in flight
             else wave_sync();
         }
@@ -226,29 +212,27 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_records(const uint8_
             next_mx = left_image(hn, wkl);
         }
         wave_sync();                                      // the landing area has been read: the right fields' now
-        key_to_lds(land, lane, ndw, right);
+        key_to_lds(W.land, lane, ndw, right);
         wave_sync();
-        // z = cent(INV(..) + sR): |.| < 2^32 is inside fz_cent's bound whatever the field held.  Range-checked in the two-halves
-        // form (see sign_encode), packed
+        // z = cent(INV(..) + sR): |.| < 2^32 is inside fz_cent's bound whatever the field held.  Range-checked, packed
         uint32_t u[16], hi = 0, mx = 0;
         {
             uint32_t ur[16];
-            key_mx = max(key_mx, key_unpack(land, lane, hc, wkl, ur));
+            key_mx = max(key_mx, key_unpack(W.land, lane, hc, wkl, ur));
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
-                const int z = (int)fz_cent((double)v[k] + (double)(int)(ur[k] - kb), m);
-                const unsigned long long s = (unsigned long long)((long long)z + (long long)bnd);
-                hi |= (uint32_t)(s >> 32);
-                mx = max(mx, (uint32_t)s);
-                u[k] = (uint32_t)s & wmask;               // a refused field stays inside its own w bits
+                const long long z = (int)fz_cent((double)v[k] + (double)(int)(ur[k] - kb), m);
+                u[k] = range_field(z, B, hi, mx);
             }
         }
-        const bool bad = hi != 0 || mx > two_b;
+        const bool bad = hi != 0 || mx > B.two_b;
         wave_sync();                                      // the landing area has been read: it is the packed chunk's now
+        // (fields_pack and the read-back stay written out: inside a helper the packing comes out longer, docs/HISTORY.md section V)
         fields_pack(reinterpret_cast<uint16_t *>(W.pk) + lane * wl, u, wl);
         wave_sync();
         const Packed o = packed_from_lds(W.pk, wl, lane);
         wave_sync();
+        // store_and_flag's two steps with the key's verdict between them: the encoding comes first
         packed_store(out, task, total_bytes, wl, lane, o);
         const bool valid = is_valid();
         records_flag(status, walk.rec, key_mx > two_kb && valid, FZ_VERDICT_ENCODING, lane);
@@ -256,17 +240,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void sign_records(const uint8_
         walk.step();
         key_mx = next_mx;
     };
-    size_t task = first;
-    for (; task + stride < tasks; task += stride) iteration(task, std::true_type());
+    size_t task = T.first;
+    for (; task + T.stride < T.tasks; task += T.stride) iteration(task, std::true_type());
     iteration(task, std::false_type());
 }
 
 template <int LOGD, bool FAST>
 void launch_sign_records(fz_ctx *ctx, const uint8_t *key, const int32_t *c_hat, uint8_t *bytes, size_t total, unsigned rv, int wk,
                          int key_bound, int w, int bound, int *d_status) {
-    const size_t tasks = (total + kChunk - 1) / kChunk, blocks = (tasks + kWavesPerBlock - 1) / kWavesPerBlock;
-    const size_t cap = (size_t)ctx->grid_signrec;
-    hipLaunchKernelGGL((sign_records<LOGD, FAST>), dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(64 * kWavesPerBlock), 0, ctx->stream,
+    hipLaunchKernelGGL((sign_records<LOGD, FAST>), chunk_grid(total, ctx->grid_signrec), dim3(64 * kWavesPerBlock), 0, ctx->stream,
                        key, c_hat, bytes, total, rv, wk, key_bound, w, bound, d_status, (const double2 *)ctx->d_twB,
                        (const double2 *)ctx->d_itwB, (const FzTwA *)ctx->d_twAB, ctx->mod);
 }
@@ -280,19 +262,16 @@ int fz_sign_records_query_grid(fz_ctx *ctx) {
     });
 }
 
-// fz_sign_records_async: d_status cleared, the fused pass over the batch, then the zeroing of refused records (fz_records.hip's).
-// Asynchronous and allocation-free: a graph capture records all three.
+// fz_sign_records_async: the fused pass over the batch as a fz_records_pass
 int fz_launch_sign_records(fz_ctx *ctx, const uint8_t *key_bytes, int wk, int64_t key_bound, const int32_t *c_hat, size_t n, int l,
                            int w, int64_t bound, uint8_t *d_bytes, int *d_status) {
     const unsigned rv = (unsigned)l * (unsigned)ctx->degree;
     const size_t total = n * rv;
-    int rc = fz_check_hip(hipMemsetAsync(d_status, 0, n * sizeof(int), ctx->stream), "records status clear");
-    if (rc != FZ_OK) return rc;
-    rc = fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
-        launch_sign_records<logd(), fast()>(ctx, key_bytes, c_hat, d_bytes, total, rv, wk, (int)key_bound, w, (int)bound, d_status);
-        return FZ_OK;
-    });
-    if (rc == FZ_OK) rc = fz_check_hip(hipGetLastError(), "sign_records launch");
-    if (rc != FZ_OK) return rc;
-    return fz_launch_records_zero(ctx, d_status, n, d_bytes, fz_record_bytes(ctx->degree, l, w));
+    const auto launch = [&]() {
+        return fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
+            launch_sign_records<logd(), fast()>(ctx, key_bytes, c_hat, d_bytes, total, rv, wk, (int)key_bound, w, (int)bound, d_status);
+            return FZ_OK;
+        });
+    };
+    return fz_records_pass(ctx, d_status, n, "sign_records launch", launch, d_bytes, fz_record_bytes(ctx->degree, l, w));
 }

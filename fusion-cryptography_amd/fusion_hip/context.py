@@ -593,12 +593,8 @@ class Context:
         bytes of sign_core's signatures under `bound` in one pass (sign_encoded_async_dev), codes 0 or 4."""
         sk, c = _as_i32(sk_hat), _as_i32(c_hat)
         batch, _, l, d = sk.shape
-        rb = l * d * (2 * int(bound)).bit_length() // 8
-        with DeviceScope() as s:
-            dK, dC = self._staged(s, [sk, c.reshape(batch, d)])
-            dB, dV = self._scratch(s, max(1, batch * rb)), self._scratch(s, max(1, batch * 4))
-            self.sign_encoded_async_dev(dK.ptr, dC.ptr, batch, l, int(bound), dB.ptr, dV.ptr)
-            return dB.to_numpy(np.uint8, (batch, rb)), dV.to_numpy(np.int32, (batch,))
+        return self._sign_bytes(c.reshape(batch, d), l, bound, lambda s: self._staged(s, [sk])[0],
+                                lambda dK, dC, dB, dV: self.sign_encoded_async_dev(dK, dC, batch, l, int(bound), dB, dV))
 
     def sign_records(self, key_bytes, key_bound, c_hat, l, bound):
         """key_bytes: batch "secret" records of [2][l][d] fields under key_bound (uint8, [batch][2 * l * d * wk / 8] or flat);
@@ -609,16 +605,23 @@ class Context:
         c = c.reshape(-1, d)
         batch, l = c.shape[0], int(l)
         kb = 2 * l * d * (2 * int(key_bound)).bit_length() // 8
-        rb = l * d * (2 * int(bound)).bit_length() // 8
         key = np.ascontiguousarray(np.frombuffer(key_bytes, dtype=np.uint8) if isinstance(key_bytes, (bytes, bytearray, memoryview))
                                    else key_bytes)
         if key.dtype != np.uint8 or key.size != batch * kb:
             raise FusionHipError(FZ_E_BADARG, f"{key.size} bytes of {key.dtype}: {batch} uint8 records of {kb} bytes expected")
+        return self._sign_bytes(c, l, bound, lambda s: s.own(DeviceBuffer.from_numpy(self, key.reshape(batch, kb))),
+                                lambda dK, dC, dB, dV: self.sign_records_async_dev(dK, int(key_bound), dC, batch, l, int(bound), dB, dV))
+
+    def _sign_bytes(self, c, l, bound, key_dev, launch):
+        """the tail sign_encoded and sign_records share, c = c_hat [batch][d]: in one DeviceScope the key (key_dev(scope)) and the
+        challenges on the device, the output and status buffers, launch(key, challenges, bytes, status), and both downloaded"""
+        batch, d = c.shape
+        rb = l * d * (2 * int(bound)).bit_length() // 8
         with DeviceScope() as s:
-            dK = s.own(DeviceBuffer.from_numpy(self, key.reshape(batch, kb)))
+            dK = key_dev(s)
             dC, = self._staged(s, [c])
             dB, dV = self._scratch(s, max(1, batch * rb)), self._scratch(s, max(1, batch * 4))
-            self.sign_records_async_dev(dK.ptr, int(key_bound), dC.ptr, batch, l, int(bound), dB.ptr, dV.ptr)
+            launch(dK.ptr, dC.ptr, dB.ptr, dV.ptr)
             return dB.to_numpy(np.uint8, (batch, rb)), dV.to_numpy(np.int32, (batch,))
 
     def aggregate_core(self, sig, alpha_hat):

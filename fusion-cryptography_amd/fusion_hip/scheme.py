@@ -318,28 +318,14 @@ class BatchScheme:
         the pass moves at secpar 256) never exist on the device.
         An sk_hat that is not [N][2][l][d] for N = the number of messages = the number of keys raises
         FusionHipError(FZ_E_BADARG) before the device is touched."""
-        _, _, bound, _, rb = _encoding(self.params, "signature")
         shape = tuple(sk_hat.shape if isinstance(sk_hat, DeviceArray) else np.shape(sk_hat))
         if len(shape) != 4 or shape[1:] != (2, self.l, self.d):
             raise FusionHipError(FZ_E_BADARG, f"sk_hat of shape {shape}: [N][2][{self.l}][{self.d}] expected")
         if isinstance(sk_hat, DeviceArray) and sk_hat.dtype != np.int32:
             raise FusionHipError(FZ_E_BADARG, f"device array of {sk_hat.dtype}: int32 expected")
         n = int(shape[0])
-        try:
-            nk = self._signer_count(vk)
-        except ValueError:
-            nk = -1
-        if not (nk == len(messages) == n):
-            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} rows of sk_hat")
-        if n == 0:
-            return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
-        with DeviceScope() as s:
-            dC = self._challenges_both(vk, messages, want_host=False, scope=s)[0]
-            dK = self._take(s, sk_hat, (n, 2, self.l, self.d))
-            dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
-            self.ctx.sign_encoded_async_dev(dK.ptr, dC.ptr, n, self.l, bound, dB.ptr, dV.ptr)
-            codes = dV.numpy()
-            return (s.release(dB) if device else dB.numpy()), codes
+        return self._sign_to_bytes(n, "rows of sk_hat", vk, messages, device, lambda s: self._take(s, sk_hat, (n, 2, self.l, self.d)),
+                                   lambda dK, dC, bound, dB, dV: self.ctx.sign_encoded_async_dev(dK, dC, n, self.l, bound, dB, dV))
 
     def sign_batch_records(self, secret, vk, messages, device=False):
         """sign_batch_encoded straight from the keys' compact bytes: `secret` holds N "secret" records
@@ -356,21 +342,29 @@ class BatchScheme:
         `device`, as sign_batch_encoded does: the call then needs no device, which a DeviceArray would (decode, which is
         given its device by the caller's choice of `device`, returns an empty DeviceArray there)."""
         _, _, key_bound, _, kb = _encoding(self.params, "secret")
-        _, _, bound, _, rb = _encoding(self.params, "signature")
         secret, n = _records_input("secret", secret, kb)
+        return self._sign_to_bytes(n, "secret records", vk, messages, device, lambda s: self._records_dev(s, secret, n, kb),
+                                   lambda dK, dC, bound, dB, dV: self.ctx.sign_records_async_dev(dK, key_bound, dC, n, self.l, bound, dB, dV))
+
+    def _sign_to_bytes(self, n, keys_are, vk, messages, device, key_dev, launch):
+        """what sign_batch_encoded and sign_batch_records share once the key's own checks gave its N = n (`keys_are`: what n counts,
+        for the message): the count check, the empty answer, and in one DeviceScope the challenges, the key on the device
+        (key_dev(scope)), the output and status buffers, launch(key, challenges, bound, bytes, status), the codes, and the
+        bytes released or downloaded"""
+        _, _, bound, _, rb = _encoding(self.params, "signature")
         try:
             nk = self._signer_count(vk)
         except ValueError:
             nk = -1
         if not (nk == len(messages) == n):
-            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} secret records")
+            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {len(messages)} messages, {n} {keys_are}")
         if n == 0:
             return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32)
         with DeviceScope() as s:
             dC = self._challenges_both(vk, messages, want_host=False, scope=s)[0]
-            dK = self._records_dev(s, secret, n, kb)
+            dK = key_dev(s)
             dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
-            self.ctx.sign_records_async_dev(dK.ptr, key_bound, dC.ptr, n, self.l, bound, dB.ptr, dV.ptr)
+            launch(dK.ptr, dC.ptr, bound, dB.ptr, dV.ptr)
             codes = dV.numpy()
             return (s.release(dB) if device else dB.numpy()), codes
 

@@ -35,6 +35,19 @@ def asm(unit):
             return fh.read()
 
 
+def assert_fits_transforms(kernels, logd_re, lds_of):
+    """what every unit built on the transforms' LDS is held to, for `kernels` = {mangled name: metadata}: no spill, no scratch,
+    and for a kernel whose name gives its degree (group 1 of `logd_re`) no more LDS than the largest kernel of
+    fz_transforms matching `lds_of` at that degree"""
+    lds = {k: v["lds"] for k, v in metadata(asm("fz_transforms"), lds_of).items()}
+    for name, f in kernels.items():
+        assert f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0 and f["private_segment_fixed_size"] == 0, (name, f)
+        logd = re.search(logd_re, name)
+        if logd:
+            same = [v for k, v in lds.items() if f"16ILi{logd.group(1)}E" in k]
+            assert same and f["lds"] <= max(same), (name, f["lds"], same)
+
+
 def bodies(text, needle):
     """{mangled name: [instructions]} of every kernel whose name contains `needle`"""
     out = {}

@@ -176,15 +176,9 @@ def test_spec_decode_is_the_forward_transform_of_the_fields():
 def test_record_kernels_compile_without_spills():
     """records_encode / records_decode / records_zero_failed: degrees 64 and 256 x both multiplies for the coefficient kinds, one
     instantiation each for keys; no spill, no scratch, and no more LDS than the transforms (lds16_doubles)"""
-    from _isa import asm, metadata
+    from _isa import asm, assert_fits_transforms, metadata
     records = metadata(asm("fz_records"), "records_")
     assert len([k for k in records if "records_encode" in k]) == 5, sorted(records)
     assert len([k for k in records if "records_decode" in k]) == 5, sorted(records)
     assert len([k for k in records if "records_zero_failed" in k]) == 1, sorted(records)
-    lds = {k: v["lds"] for k, v in metadata(asm("fz_transforms"), "ntt_inv16|ntt_fwd16").items()}
-    for name, f in records.items():
-        assert f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0 and f["private_segment_fixed_size"] == 0, (name, f)
-        logd = re.search(r"records_(?:encode|decode)ILi(\d)E", name)
-        if logd:
-            same = [v for k, v in lds.items() if f"16ILi{logd.group(1)}E" in k]
-            assert same and f["lds"] <= max(same), (name, f["lds"], same)
+    assert_fits_transforms(records, r"records_(?:encode|decode)ILi(\d)E", "ntt_inv16|ntt_fwd16")

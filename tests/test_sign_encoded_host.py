@@ -43,18 +43,13 @@ def test_new_unit_has_four_kernels_without_spills_within_the_transforms_lds():
     """fz_sign_encoded: sign_encode for degrees 64 and 256 x both multiply forms, nothing else; no spill, no scratch, no more
     LDS than ntt_inv16 of the same degree"""
     import __graft_entry__ as GE
-    from _isa import asm, metadata
+    from _isa import asm, assert_fits_transforms, metadata
     assert "fz_sign_encoded.hip" in GE.SOURCES
     unit = metadata(asm("fz_sign_encoded"))
     assert len(unit) == 4, sorted(unit)
     assert sorted(re.search(r"\d+sign_encodeILi(\d)ELb(\d)E", k).groups() for k in unit) == \
         [("6", "0"), ("6", "1"), ("8", "0"), ("8", "1")], sorted(unit)
-    lds = {k: v["lds"] for k, v in metadata(asm("fz_transforms"), "ntt_inv16").items()}
-    for name, f in unit.items():
-        assert f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0 and f["private_segment_fixed_size"] == 0, (name, f)
-        logd = re.search(r"sign_encodeILi(\d)E", name).group(1)
-        same = [v for k, v in lds.items() if f"16ILi{logd}E" in k]
-        assert same and f["lds"] <= max(same), (name, f["lds"], same)
+    assert_fits_transforms(unit, r"sign_encodeILi(\d)E", "ntt_inv16")          # (every kernel has a degree: the line above)
 
 
 def test_the_entry_is_declared_and_has_a_signature():

@@ -6,8 +6,8 @@
 Each side is a set of `.s` files (hipcc -S --cuda-device-only with the build's flags); a kernel is looked up by its mangled name
 in whichever file of a side holds it.  Compared per kernel: the instruction list (block labels `.LBB<n>_<m>` normalised: their
 function index depends on what else the file holds) and the resource figures of the metadata: vgpr_count, sgpr_count, LDS,
-scratch, spills.  Reported: equal / different per kernel with the sizes, a summary per kernel family, and the kernels only one
-side has."""
+scratch, spills.  Reported: equal / different per kernel with the sizes (and whether the difference is only the order of source operands,
+instruction by instruction), a summary per kernel family, and the kernels only one side has."""
 import argparse
 import collections
 import re
@@ -42,6 +42,21 @@ def kernels(paths):
     return out
 
 
+COMMUTATIVE = re.compile(r"^[sv]_(add_f\d+|mul_f\d+|mul_lo_u32|mul_hi_u32|mul_i32|add_u32|add_i32|and_b\d+|or_b\d+|xor_b\d+|max_[fiu]\d+|min_[fiu]\d+)(_e32|_e64)?$")
+
+
+def exchanged_only(ia, ib):
+    """do the two instruction lists differ in nothing but the order of the two source operands of commutative instructions,
+    instruction by instruction?"""
+    def same(x, y):
+        if x == y:
+            return True
+        (ox, _, rx), (oy, _, ry) = x.partition(" "), y.partition(" ")
+        ax, ay = rx.split(", "), ry.split(", ")
+        return ox == oy and bool(COMMUTATIVE.match(ox)) and len(ax) == 3 and ax[0] == ay[0] and ax[1:] == ay[:0:-1]
+    return len(ia) == len(ib) and all(same(x, y) for x, y in zip(ia, ib))
+
+
 def family(name):
     """the kernel's own name out of its mangled one (an anonymous namespace in front or not)"""
     m = re.match(r"_ZN?(?:12_GLOBAL__N_1)?(\d+)", name)
@@ -61,7 +76,9 @@ def main():
         fam[family(name)][0 if same else 1] += 1
         if not same:
             what = " ".join(f"{k} {ma[k]}->{mb[k]}" for k in ma if ma[k] != mb[k])
-            print(f"DIFFERENT {name}: {len(ia)} -> {len(ib)} instructions{'; ' + what if what else ''}")
+            swaps = sum(x != y for x, y in zip(ia, ib)) if ma == mb and exchanged_only(ia, ib) else 0
+            note = f"; the two source operands of {swaps} commutative instructions exchanged, nothing else" if swaps else ""
+            print(f"DIFFERENT {name}: {len(ia)} -> {len(ib)} instructions{'; ' + what if what else ''}{note}")
     for side, only in (("first", sorted(set(A) - set(B))), ("second", sorted(set(B) - set(A)))):
         for name in only:
             print(f"ONLY IN THE {side.upper()} BUILD {name}")
