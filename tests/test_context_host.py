@@ -1,117 +1,22 @@
 """The lifetime logic of a context (csrc/fz_context.hip, csrc/fz_diag.hip) without a GPU: the two units are compiled for the host
-with AddressSanitizer + UndefinedBehaviorSanitizer and linked, as a stand-alone program, against a stub HIP runtime that this
-file carries.  The stub backs device and pinned memory with malloc / free and streams, events and graphs with small heap
+with AddressSanitizer + UndefinedBehaviorSanitizer and linked, as a stand-alone program, against the stub HIP runtime of
+tests/_hip_stub.py.  The stub backs device and pinned memory with malloc / free and streams, events and graphs with small heap
 objects, logs every call with its arguments and has two controls: "the stream is capturing" and "the k-th allocation (or event
 creation) fails".  The driver asserts the one rule of the growable areas from that log (fit, growth, capacities, zeroing, retire
 after a capture, refusal during one, the dirty re-zero), that fz_ctx_destroy misses nothing (leak detection reports a stub
 allocation that is never released, ASan a double free) and that every allocation site of the two units may be the failing one."""
 import os
 import re
-import shutil
 import subprocess
 
-import pytest
+from _hip_stub import CSRC, STUB, build_driver, toolchain
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "fusion-cryptography_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-HOSTCXX = os.environ.get("HOSTCXX", "/opt/rocm/lib/llvm/bin/clang++")
 UNITS = ("fz_context", "fz_diag")
 # what fz_last_error() names when an allocation of the two units fails: one entry per site (the areas share fz_area_replace)
 ALLOC_WHATS = {"table alloc", "verdict alloc", "scratch alloc", "scratch2 alloc", "verify scratch alloc", "verify state alloc",
                "aggregation scratch alloc", "challenge table alloc", "stamp buffer alloc", "diag alloc", "hipMalloc", "event create"}
 
-DRIVER = r'''
-#include "fz_internal.h"
-#include "fusion_hip.h"
-#include "fusion_hip_diag.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <set>
-#include <string>
-#include <vector>
-
-// ---- the stub runtime ------------------------------------------------------------------------------------------------
-struct ihipStream_t { int capturing; };
-struct ihipEvent_t { int recorded; };
-struct ihipGraph { int nodes; };
-struct hipGraphExec { int nodes; };
-struct Call { std::string fn; const void *p; size_t n; const void *stream; };
-static std::vector<Call> g_log;
-static bool g_report_capture = false;                 // control: hipStreamIsCapturing reports an active capture
-static long g_fail_at = -1, g_allocs = 0;             // control: allocations [g_fail_at, g_fail_at + g_fail_n) fail
-static int g_fail_n = 1;
-static long g_fail_event_at = -1, g_events = 0;       // ... and this event creation
-static void rec(const char *fn, const void *p = nullptr, size_t n = 0, const void *stream = nullptr) { g_log.push_back({fn, p, n, stream}); }
-static bool alloc_fails() { const long k = g_allocs++; return g_fail_at >= 0 && k >= g_fail_at && k < g_fail_at + g_fail_n; }
-static hipError_t new_event(hipEvent_t *e) {
-    if (g_events++ == g_fail_event_at) { *e = nullptr; return hipErrorOutOfMemory; }
-    *e = new ihipEvent_t{0};
-    rec("hipEventCreate", *e);
-    return hipSuccess;
-}
-static hipError_t new_stream(hipStream_t *s) { *s = new ihipStream_t{0}; rec("hipStreamCreate", *s); return hipSuccess; }
-extern "C" {
-const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "stub error"; }
-hipError_t hipGetLastError(void) { return hipSuccess; }
-hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipRuntimeGetVersion(int *v) { *v = HIP_VERSION; return hipSuccess; }
-hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
-    memset(p, 0, sizeof(*p));
-    p->multiProcessorCount = 256;
-    snprintf(p->gcnArchName, sizeof(p->gcnArchName), "gfx950:sramecc+:xnack-");
-    return hipSuccess;
-}
-hipError_t hipMalloc(void **p, size_t n) {
-    if (alloc_fails()) { rec("hipMalloc failed", nullptr, n); return hipErrorOutOfMemory; }
-    *p = malloc(n ? n : 1);
-    rec("hipMalloc", *p, n);
-    return hipSuccess;
-}
-hipError_t hipFree(void *p) { rec("hipFree", p); free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void **p, size_t n, unsigned) {
-    if (alloc_fails()) { rec("hipHostMalloc failed", nullptr, n); return hipErrorOutOfMemory; }
-    *p = malloc(n ? n : 1);
-    rec("hipHostMalloc", *p, n);
-    return hipSuccess;
-}
-hipError_t hipHostFree(void *p) { rec("hipHostFree", p); free(p); return hipSuccess; }
-hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { rec("hipMemcpy", d, n); memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t st) { rec("hipMemcpyAsync", d, n, st); memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st) { rec("hipMemsetAsync", d, n, st); if (n) memset(d, v, n); return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t st) { rec("hipStreamSynchronize", nullptr, 0, st); return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return new_stream(s); }
-hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { return new_stream(s); }
-hipError_t hipDeviceGetStreamPriorityRange(int *least, int *greatest) { *least = 0; *greatest = -1; return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { rec("hipStreamDestroy", s); delete s; return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t e, unsigned) { rec("hipStreamWaitEvent", e, 0, st); return hipSuccess; }
-hipError_t hipStreamBeginCapture(hipStream_t st, hipStreamCaptureMode) { rec("hipStreamBeginCapture", nullptr, 0, st); st->capturing = 1; return hipSuccess; }
-hipError_t hipStreamEndCapture(hipStream_t st, hipGraph_t *g) { rec("hipStreamEndCapture", nullptr, 0, st); st->capturing = 0; *g = new ihipGraph{1}; return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t st, hipStreamCaptureStatus *out) {
-    *out = (g_report_capture || st->capturing) ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
-    return hipSuccess;
-}
-hipError_t hipGraphInstantiate(hipGraphExec_t *ex, hipGraph_t, hipGraphNode_t *, char *, size_t) { *ex = new hipGraphExec{1}; return hipSuccess; }
-hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t st) { rec("hipGraphLaunch", nullptr, 0, st); return hipSuccess; }
-hipError_t hipGraphExecDestroy(hipGraphExec_t ex) { delete ex; return hipSuccess; }
-hipError_t hipGraphDestroy(hipGraph_t g) { delete g; return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { return new_event(e); }
-hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return new_event(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { rec("hipEventDestroy", e); delete e; return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t st) { rec("hipEventRecord", e, 0, st); e->recorded = 1; return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t e) { rec("hipEventSynchronize", e); return hipSuccess; }
-hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 1.0f; return hipSuccess; }
-}
-// what the two units take from the kernel units
-int fz_ntt_query_grid(fz_ctx *) { return FZ_OK; }
-int fz_aggregate_encoded_query_grid(fz_ctx *) { return FZ_OK; }
-int fz_launch_diag(fz_ctx *, int, const void *, void *, size_t) { return FZ_OK; }
-int fz_launch_diag_clock(hipStream_t, unsigned long long, unsigned long long *) { return FZ_OK; }
-unsigned fz_multi_plan(const FzMultiJobs &, int, const FzProduced *, int, bool, unsigned, int *, unsigned *, int *, int *) { return 0; }
-
+DRIVER = STUB + r'''
 // ---- the driver ------------------------------------------------------------------------------------------------------
 #define CHECK(cond) do { if (!(cond)) { printf("FAILED line %d: %s   (last error: %s)\n", __LINE__, #cond, fz_last_error()); exit(1); } } while (0)
 static const uint32_t Q = 2147465729u;
@@ -357,24 +262,11 @@ int main() {
 
 
 def test_context_lifetime_under_asan_ubsan_and_leak_detection(tmp_path):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    hostcxx = HOSTCXX if os.path.exists(HOSTCXX) else "clang++"
-    san = "-fsanitize=address,undefined"
-    objs = []
-    for unit in UNITS:
-        objs.append(str(tmp_path / (unit + ".o")))
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-Xarch_host", san,
-                               "-c", os.path.join(CSRC, unit + ".hip"), "-o", objs[-1]])
+    toolchain()                                               # (skips without hipcc)
     # a new allocation site in the two units has to become the failing one in the script (and be named in ALLOC_WHATS)
     text = "".join(open(os.path.join(CSRC, unit + ".hip")).read() for unit in UNITS)
     assert len(re.findall(r"\bhip(?:Host)?Malloc\w*\(", text)) == 5, "allocation sites changed: extend the driver's script"
-    src = tmp_path / "driver.cpp"
-    src.write_text(DRIVER)
-    exe = tmp_path / "driver"
-    rocm = os.path.dirname(os.path.dirname(shutil.which(HIPCC) or HIPCC))
-    subprocess.check_call([hostcxx, "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"), "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                           "-std=c++17", "-O1", "-g", san, "-fno-sanitize-recover=all", "-pthread", str(src)] + objs + ["-o", str(exe)])
+    exe = build_driver(tmp_path, UNITS, DRIVER, "-fsanitize=address,undefined", flags=["-fno-sanitize-recover=all"])
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]

@@ -265,3 +265,95 @@ def test_queued_aggregates_mixed_with_keygen_sign_and_the_capacity_verdict():
         assert bq.wait_verdict(bq.submit_verify(vk[a:b], msgs[a:b], agg4)) == (False, "Too many keys.")
         assert bq.wait_verdict(bq.submit_verify(vk[a:a + 3], msgs[a:a + 3], bs.aggregate(vk[a:a + 3], msgs[a:a + 3], sig[a:a + 3]))) == (True, "")
     bs.close()
+
+
+def test_the_cut_at_max_rows_on_the_device():
+    """workers=1, max_rows=8, calls of 3, 5, 1, 8, 2, 7, 1 keys back to back: however the worker's timing cuts what is pending into
+    batches (a batch is a run of consecutive calls of at most max_rows keys -- between the greedy minimum and one batch per call),
+    every call's rows are keygen_batch + sign_batch of that call alone"""
+    import fusion.fusion as F
+    from fusion_hip.queue import BatchQueue
+    from fusion_hip.scheme import BatchScheme
+    params = F.fusion_setup(128, 11)
+    bs = BatchScheme(params)
+    sizes, max_rows = [3, 5, 1, 8, 2, 7, 1], 8
+    calls = [([1000 * k + i for i in range(n)], [f"call {k} key {i} " + "y" * (5 * k + i) for i in range(n)]) for k, n in enumerate(sizes)]
+    with BatchQueue(params, workers=1, max_rows=max_rows) as bq:
+        tickets = [bq.submit_keygen_sign(seeds, msgs, keep_sk=(k % 2 == 0)) for k, (seeds, msgs) in enumerate(calls)]
+        for k, ((seeds, msgs), t) in enumerate(zip(calls, tickets)):
+            r = bq.wait(t)
+            sk, vk = bs.keygen_batch(seeds)
+            assert r.n == len(seeds) and np.array_equal(r.vk, vk), k
+            assert np.array_equal(r.signatures(), bs.sign_batch(sk, vk, msgs)), k
+            if k % 2 == 0:
+                assert np.array_equal(r.secret_keys(), sk), k
+            r.release()
+        done, batches, rows = bq.stats()
+    fewest, run = 0, 0                                     # the greedy consecutive-run minimum
+    for n in sizes:
+        if fewest == 0 or run + n > max_rows:
+            fewest, run = fewest + 1, n
+        else:
+            run += n
+    assert fewest == 5                                     # {3, 5} {1} {8} {2} {7, 1}
+    assert done == 7 and rows == 27 and fewest <= batches <= 7, (done, batches, rows)
+    bs.close()
+
+
+def test_queued_verification_of_an_aggregate_on_the_device():
+    """submit_verify with the aggregate in device memory (FZ_QUEUE_ROWS_ON_DEVICE for the verify kind): the queued aggregate of
+    5 signers verifies from a DeviceArray, the same rows with one coefficient + 1 do not"""
+    import fusion.fusion as F
+    import fusion_hip
+    from fusion_hip.context import VERDICT_REASONS
+    from fusion_hip.queue import BatchQueue
+    from fusion_hip.scheme import BatchScheme
+    params = F.fusion_setup(128, 21)
+    bs = BatchScheme(params)
+    seeds = [77 * i + 3 for i in range(5)]
+    msgs = [f"signer {i}" for i in range(5)]
+    sk, vk = bs.keygen_batch(seeds)
+    sig = bs.sign_batch(sk, vk, msgs)
+    with BatchQueue(params, workers=1) as bq:
+        agg, verdict = bq.wait_aggregate(bq.submit_aggregate_verify(vk, msgs, sig))
+        assert verdict == (True, "") and np.array_equal(agg, bs.aggregate(vk, msgs, sig))
+        bad = agg.copy()
+        bad[1, 7] += 1
+        d_agg = fusion_hip.DeviceArray.from_numpy(bs.ctx, agg)
+        d_bad = fusion_hip.DeviceArray.from_numpy(bs.ctx, bad)
+        t_ok, t_bad = bq.submit_verify(vk, msgs, d_agg), bq.submit_verify(vk, msgs, d_bad)
+        assert bq.wait_verdict(t_ok) == (True, "")
+        assert bq.wait_verdict(t_bad) == (False, VERDICT_REASONS[3]) == (False, "Target doesn't match image of aggregate signature.")
+        assert bq.wait_verdict(bq.submit_verify(vk, msgs, d_agg.ptr)) == (True, "")         # a raw device pointer
+        d_agg.free()
+        d_bad.free()
+    bs.close()
+
+
+def test_discarded_calls_without_verification_keys():
+    """discard=True, want_vk=False, alone and with keep_sk=True: nothing comes back (n = 0, no pointers, no vk), drain() and
+    collect_discarded() leave the queue usable and a later kept call is right"""
+    import fusion.fusion as F
+    from fusion_hip.queue import BatchQueue
+    from fusion_hip.scheme import BatchScheme
+    params = F.fusion_setup(128, 31)
+    bs = BatchScheme(params)
+    seeds = [5 * i + 1 for i in range(6)]
+    msgs = [f"discarded {i}" for i in range(6)]
+    with BatchQueue(params, workers=1, max_rows=64) as bq:
+        for keep_sk in (False, True):
+            r = bq.wait(bq.submit_keygen_sign(seeds, msgs, keep_sk=keep_sk, discard=True, want_vk=False))
+            assert r.n == 0 and r.vk is None and not r.sig_ptr and not r.vk_ptr and not r.sk_ptr
+            r.release()
+        t = bq.submit_keygen_sign(seeds, msgs, discard=True, want_vk=False)                  # nobody waits for this one
+        bq.drain()
+        bq.collect_discarded()
+        assert bq.stats() == (3, 3, 18)                    # (each call had finished before the next was submitted)
+        r = bq.wait(bq.submit_keygen_sign(seeds, msgs, keep_sk=True))
+        sk, vk = bs.keygen_batch(seeds)
+        assert r.n == 6 and np.array_equal(r.vk, vk) and np.array_equal(r.secret_keys(), sk)
+        assert np.array_equal(r.signatures(), bs.sign_batch(sk, vk, msgs))
+        r.release()
+        assert bq.wait(t).n == 0
+        bq.drain()
+    bs.close()
