@@ -27,7 +27,10 @@ unsigned grid_for(fz_ctx *ctx, size_t work_items, int per_cu = -1) {
     size_t blocks = (work_items + kBlock - 1) / kBlock;
     // default: a flat grid, one item per thread (45.0 us per 1024 signatures for sign_core against 49.7 with the grid capped at
     // 8 workgroups per CU, cold: round 2)
-    size_t cap = per_cu > 0 ? (size_t)ctx->num_cu * per_cu : (size_t)0x7fffffff;
+    // A launch's threads, gridDim.x * blockDim.x, must stay below 2^32: the runtime refuses a product of exactly 2^32 ("invalid
+    // configuration argument": 2^32 items, a fill of 16 GiB) and takes it mod 2^32 beyond.  Every caller walks its items with a
+    // grid-stride loop, so the flat grid ends there.
+    size_t cap = per_cu > 0 ? (size_t)ctx->num_cu * per_cu : (size_t)0xffffffffu / kBlock;
     if (blocks < 1) blocks = 1;
     return (unsigned)(blocks < cap ? blocks : cap);
 }

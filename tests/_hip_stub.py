@@ -3,8 +3,9 @@ tests/test_queue_host.py: STUB is C++ text that a driver program starts with.  D
 AddressSanitizer sees a read of a block that was released too early, and leak detection a block that never was), streams, events
 and graphs are small heap objects.  Every call is logged under a mutex with its pointer, size, stream, source pointer and copy
 kind, a global sequence number (stub_seq(): a driver may stamp records of its own from the same counter) and a small integer
-naming the calling thread (stub_tid()).  Controls: "the stream is capturing" and "the k-th allocation (or event creation)
-fails".  build_driver() compiles units of csrc host-only with a sanitizer and links them with a driver into a stand-alone program."""
+naming the calling thread (stub_tid()).  Controls: "the stream is capturing", "the k-th allocation (or event creation)
+fails", "hipMemcpy touches nothing" and "a large hipMalloc is backed by one byte" (drivers that hand over dummy pointers).
+build_driver() compiles units of csrc host-only with a sanitizer and links them with a driver into a stand-alone program."""
 import os
 import shutil
 import subprocess
@@ -45,6 +46,8 @@ static bool g_report_capture = false;                 // control: hipStreamIsCap
 static long g_fail_at = -1, g_allocs = 0;             // control: allocations [g_fail_at, g_fail_at + g_fail_n) fail
 static int g_fail_n = 1;
 static long g_fail_event_at = -1, g_events = 0;       // ... and this event creation
+static bool g_copy_nothing = false;                   // control: hipMemcpy logs and touches no memory (a driver whose pointers are dummies)
+static size_t g_fake_above = 0;                       // control: a hipMalloc of more bytes than this (0: never) is logged with its size, backed by 1 byte
 static int stub_tid() {
     static std::atomic<int> next(0);
     static thread_local int id = next++;
@@ -98,7 +101,7 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) {
 }
 hipError_t hipMalloc(void **p, size_t n) {
     if (alloc_fails()) { rec("hipMalloc failed", nullptr, n); return hipErrorOutOfMemory; }
-    *p = malloc(n ? n : 1);
+    *p = malloc(g_fake_above && n > g_fake_above ? 1 : (n ? n : 1));
     rec("hipMalloc", *p, n, nullptr, nullptr, -1, 1);
     return hipSuccess;
 }
@@ -110,7 +113,7 @@ hipError_t hipHostMalloc(void **p, size_t n, unsigned) {
     return hipSuccess;
 }
 hipError_t hipHostFree(void *p) { rec("hipHostFree", p, 0, nullptr, nullptr, -1, p ? -1 : 0); free(p); return hipSuccess; }
-hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { rec("hipMemcpy", d, n, nullptr, s, (int)k); memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { rec("hipMemcpy", d, n, nullptr, s, (int)k); if (!g_copy_nothing) memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) { rec("hipMemcpyAsync", d, n, st, s, (int)k); memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st) { rec("hipMemsetAsync", d, n, st); if (n) memset(d, v, n); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t st) { rec("hipStreamSynchronize", nullptr, 0, st); return hipSuccess; }
@@ -161,9 +164,22 @@ def sanitizer_links(tmp_path, san):
     return subprocess.run([hostcxx, san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode == 0
 
 
-def build_driver(tmp_path, units, driver_text, san, name="driver", sources=(), flags=()):
+def fatbin_definitions(objs):
+    """C++ text that defines the fat-binary symbol each host-only object of a unit WITH kernels refers to (its registration code
+    takes the symbol's address; a stub runtime never reads it)"""
+    _, hostcxx, _ = toolchain()
+    nm = os.path.join(os.path.dirname(hostcxx), "llvm-nm")
+    names = set()
+    for obj in objs:
+        out = subprocess.check_output([nm if os.path.exists(nm) else "nm", "-u", obj], text=True)
+        names.update(line.split()[-1] for line in out.splitlines() if "__hip_fatbin_" in line)
+    return "".join('extern "C" { extern const char %s[16]; const char %s[16] = {0}; }\n' % (n, n) for n in sorted(names))
+
+
+def build_driver(tmp_path, units, driver_text, san, name="driver", sources=(), flags=(), late_text=None):
     """units of csrc compiled host-only (hipcc) with `san`, linked with the driver (STUB + the test's own code) and `sources`
-    (plain C++ files of csrc) -> path of the program"""
+    (plain C++ files of csrc) -> path of the program.  late_text(objects) -> C++ text appended to the driver once the units are
+    compiled (fatbin_definitions, for units that hold kernels)."""
     hipcc, hostcxx, rocm = toolchain()
     objs = []
     for unit in units:
@@ -171,7 +187,7 @@ def build_driver(tmp_path, units, driver_text, san, name="driver", sources=(), f
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-Xarch_host", san,
                                "-c", os.path.join(CSRC, unit + ".hip"), "-o", objs[-1]])
     src = tmp_path / (name + ".cpp")
-    src.write_text(driver_text)
+    src.write_text(driver_text + (late_text(objs) if late_text else ""))
     exe = tmp_path / name
     subprocess.check_call([hostcxx, "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"), "-I", CSRC, "-I", os.path.join(ROOT, "include"),
                            "-std=c++17", "-O1", "-g", san, "-pthread"] + list(flags) + [str(src)] + [str(s) for s in sources] + objs + ["-o", str(exe)])

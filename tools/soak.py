@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised soak of every kernel against the CPU oracle: random batch sizes, both NTT schedules, both degrees,
 fused and multi-launch paths, two contexts on two streams interleaved and ordered by events, repeated verify launches (re-armed
-accumulators), graph replays.  usage: soak.py [seconds] [seed]   (needs an MI355X; prints a progress line per minute)"""
+accumulators), graph replays, operands that begin past 2^32 bytes inside a large allocation.  usage: soak.py [seconds] [seed]   (needs an MI355X; prints a progress line per minute)"""
 import os
 import sys
 import time
@@ -56,6 +56,7 @@ VARIANTS = [{}, {"FZ_UNFUSED": "1"}, {"FZ_AGG_DIRECT": "-1"}, {"FZ_AGG_DIRECT": 
             {"FZ_MATVEC_SLICES": "16"}, {"FZ_MATVEC_SLICES": "2"}, {"FZ_MATVEC_SLICES": "-1"}, {"FZ_POLYMUL_FORM": "2"}, {"FZ_POLYMUL_FORM": "1"}]
 vctx = {(sp, i): make_ctx(sp, "", v) for sp in (128, 256) for i, v in enumerate(VARIANTS)}
 DB = fusion_hip.DeviceBuffer
+far_arena = None                 # the `far` leg's allocation, made at its first turn
 t_end = time.time() + budget
 t_print = time.time() + 60
 it = 0
@@ -68,7 +69,7 @@ while time.time() < t_end:
     ctx = ctxs[(sp, kern)]
     other = ctxs[(sp, str(rng.choice(KERNS)))]
     rows = int(rng.choice([1, 2, 3, 5, 63, 64, 65, 257, 1000, 4099, int(rng.integers(1, 20000))]))
-    what = rng.choice(["ntt", "polymul", "scheme", "graph", "pointwise", "small", "batch_api", "multi", "challenge", "sampler", "ragged", "queue", "wide"])
+    what = rng.choice(["ntt", "polymul", "scheme", "graph", "pointwise", "small", "batch_api", "multi", "challenge", "sampler", "ragged", "queue", "wide", "far"])
     raw = rng.random() < 0.3
     x = (rng.integers(-2**31, 2**31, size=(rows, d), dtype=np.int64).astype(np.int32) if raw
          else O.splitmix_centered(int(rng.integers(1, 2**40)), rows * d).reshape(rows, d))
@@ -98,6 +99,35 @@ while time.time() < t_end:
         for b in (dx, dy, dz, ex, ey):
             b.free()
         bump("ntt")
+    elif what == "far":
+        # operands that BEGIN past 2^32 bytes inside one large allocation (made once: 4 GiB + 64 MiB): base pointers whose offset
+        # from the allocation's start needs 33 bits, for the transform and pointwise entries on every schedule
+        # The arena belongs to one context and is used from every context and stream: that is in order only because every use below
+        # ends in a synchronous d2h on the using context, so no two legs ever have work on it in flight at once.
+        if far_arena is None:
+            far_arena = DB(ctxs[(256, "")], (1 << 32) + (64 << 20))
+        rows = min(rows, 4099)
+        n = rows * d
+        slot = (n * 4 + 15) & ~15
+        base = far_arena.ptr + (1 << 32) + 16 * int(rng.integers(0, ((64 << 20) - 3 * slot) // 16))
+        pa, pb, po = base, base + slot, base + 2 * slot
+        sa, sb = (int(v) for v in rng.integers(1, 2**40, size=2))
+        ctx.fill_synthetic_dev(pa, n, sa)
+        ctx.fill_synthetic_dev(pb, n, sb)
+        a, b = O.splitmix_centered(sa, n).reshape(rows, d), O.splitmix_centered(sb, n).reshape(rows, d)
+        got = np.empty((rows, d), np.int32)
+        ctx.ntt_forward_dev(pa, po, rows)
+        assert np.array_equal(ctx.d2h(got, po), orc.ntt_forward(a, q, root).reshape(rows, d)), ("far fwd", sp, kern, rows)
+        ctx.ntt_inverse_dev(pb, po, rows)
+        assert np.array_equal(ctx.d2h(got, po), orc.ntt_inverse(b, q, inv).reshape(rows, d)), ("far inv", sp, kern, rows)
+        cut = n - int(rng.integers(0, 4))                                    # a count that need not be a multiple of 4
+        flat = got.reshape(-1)[:cut]
+        for op, ref in ((fusion_hip.OP_MUL, orc.pw_mul), (fusion_hip.OP_ADD, orc.pw_add), (fusion_hip.OP_SUB, orc.pw_sub)):
+            ctx.pw_dev(op, pa, pb, po, cut)
+            assert np.array_equal(ctx.d2h(flat, po), ref(a.reshape(-1)[:cut], b.reshape(-1)[:cut], q)), ("far pw", op, sp, cut)
+        ctx.pw_neg_dev(pa, po, cut)
+        assert np.array_equal(ctx.d2h(flat, po), orc.pw_neg(a.reshape(-1)[:cut], q)), ("far neg", sp, cut)
+        bump("far")
     elif what == "multi":
         # one dispatch over a random list of forward / inverse jobs (some in place, some empty)
         nj = int(rng.integers(1, 45))
@@ -438,4 +468,6 @@ while time.time() < t_end:
     if time.time() > t_print:
         print(f"[soak] {it} iterations ok: {counts}", flush=True)
         t_print = time.time() + 60
+if far_arena is not None:
+    far_arena.free()
 print(f"[soak] PASSED {it} iterations in {budget:.0f} s: {counts}", flush=True)
