@@ -85,6 +85,7 @@ struct fz_ctx {
     int grid_signenc;            // ... of sign_encode (fz_sign_encoded.hip; degree 64 / 256)
     int grid_aggenc_rag;         // ... of aggregate_encoded_ragged (fz_aggregate_many_encoded.hip; degree 64 / 256)
     int grid_signrec;            // ... of sign_records (fz_sign_records.hip; degree 64 / 256)
+    int grid_keyrec;             // ... of keygen_records_bcast (fz_keygen_records.hip; degree 64 / 256)
     // verification from the bytes with several workgroups per record (fz_verify_encoded.hip; degree 64 / 256): a slot of int64 sums
     // and a status word per record, venc_bytes in all; allocated once at context creation (fz_verify_encoded_setup), never grown --
     // the entry is allocation-free and capturable from its first call -- and released by fz_ctx_destroy
@@ -303,9 +304,17 @@ int fz_launch_sign_encoded(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_
 // signing straight from "secret" records to the bytes (fz_sign_records.hip; degree 64 / 256): record i of d_bytes = the encoding of
 // cent(INV(cent(FWD(sL_i) (.) c_i)) + sR_i) from key records [n][2][l][degree] of wk-bit fields s + key_bound and c_hat [n][degree], any
 // int32; d_status [n] cleared, then 0, FZ_VERDICT_NORM or FZ_VERDICT_ENCODING (a key field above 2 key_bound); refused records zeroed
-int fz_sign_records_query_grid(fz_ctx *ctx);                       // ctx->grid_signrec (context creation: fz_aggregate_many_encoded_query_grid calls it)
+int fz_sign_records_query_grid(fz_ctx *ctx);                       // ctx->grid_signrec, then fz_keygen_records_query_grid (context creation: fz_aggregate_many_encoded_query_grid calls it)
 int fz_launch_sign_records(fz_ctx *ctx, const uint8_t *key_bytes, int wk, int64_t key_bound, const int32_t *c_hat, size_t n, int l,
                            int w, int64_t bound, uint8_t *d_bytes, int *d_status);
+
+// key generation straight to "secret" records (fz_keygen_records.hip; degree 64 / 256): record i of d_bytes = the fields s + key_bound
+// (wk bits) of s = cent(coef mod q) over [2][l][degree], from coef [n][2][degree] (one polynomial per half for all l rows) or,
+// with `rows`, [n][2][l][degree]; d_vk [n][2][degree] as fz_launch_keygen_fused writes it; d_status [n] cleared, then 0 or
+// FZ_VERDICT_NORM; refused records zeroed
+int fz_keygen_records_query_grid(fz_ctx *ctx);                     // ctx->grid_keyrec (context creation: fz_sign_records_query_grid calls it)
+int fz_launch_keygen_records(fz_ctx *ctx, const int32_t *A, const int32_t *coef, bool rows, size_t n, int l, int wk, int64_t key_bound,
+                             uint8_t *d_bytes, int32_t *d_vk, int *d_status);
 
 // the byte encoding's consumers without rows (fz_aggregate_encoded.hip; degree 64 / 256): the range check of a byte stream alone
 // (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from

@@ -2,7 +2,8 @@
 // records_* kernels; fz_aggregate_encoded.hip and fz_aggregate_many_encoded.hip, through fz_aggregate_encoded_dev.h: the range check
 // and the aggregation straight from the bytes, of one committee and of many; fz_verify_encoded.hip:
 // the verification straight from the bytes; fz_sign_encoded.hip: signing straight to the bytes; fz_sign_records.hip: signing
-// straight from the key's bytes to the signature's): the packed chunk of the chunk
+// straight from the key's bytes to the signature's; fz_keygen_records.hip: key generation straight to the key's bytes, which
+// takes the field packing, the range check's step and the status flag): the packed chunk of the chunk
 // walk with its loads and stores, the field packing and unpacking, the consumers' steps from the packed chunk to the transform's
 // outputs and their sums, the per-record status flag, the record walk, the chunk walk's opening, and the producers' steps from
 // the int32 image to the stored chunk (the range check's operands and its per-value step, the inverse transform centred into the

@@ -281,6 +281,32 @@ def keygen(params: Params, seed: Optional[int]) -> OneTimeKeyTuple:
     return sk, vkey
 
 
+def keygen_to_bytes(params: Params, seed: Optional[int]) -> Tuple[bytes, OneTimeVerificationKey]:
+    """NOT in the reference: (to_bytes(params, keygen(params, seed)[0]), keygen(params, seed)[1]) without the signing key's
+    rows in between -- the secret polynomials sampled exactly as keygen() samples them (and the process-global `random` left
+    where it leaves it), then one fz_keygen_records_async call that packs them into the "secret" record and transforms them for
+    the verification key alone.  Raises ValueError with the reason when the key is over beta_sk, as to_bytes does."""
+    from fusion_hip import ENCODING_REASONS
+    q = params.modulus
+    A = _rows_of(params.public_challenge, q)
+    if seed is not None and _pristine("sample_coefficient_matrix", "transform"):
+        coef = np.stack([_sample_half(params, s) for s in (seed, seed + 1)])[None]            # [1][2][d]: see keygen()
+    else:
+        halves = []
+        for s in (seed, seed + 1):       # (raises TypeError on None + 1, as the reference does)
+            coefs = sample_coefficient_matrix(
+                seed=s, modulus=q, degree=params.degree, root_order=params.root_order, root=params.root,
+                inv_root=params.inv_root, num_rows=params.num_rows_sk, num_cols=params.num_cols_sk,
+                norm_bound=params.beta_sk, weight_bound=params.omega_sk)
+            halves.append(_rows_of(coefs, q))
+        coef = np.stack(halves)[None]                                                         # [1][2][l][d]
+    data, vk, codes = _ctx(params).keygen_records(A, coef, int(params.beta_sk))
+    if codes[0]:
+        raise ValueError(ENCODING_REASONS[int(codes[0])])
+    vkey = OneTimeVerificationKey(left_vk_hat=_column(params, vk[0, 0:1]), right_vk_hat=_column(params, vk[0, 1:2]))
+    return data.tobytes(), vkey
+
+
 class SignatureChallenge(object):
     def __init__(self, c_hat: PolynomialNTTRepresentation):
         self.c_hat = c_hat

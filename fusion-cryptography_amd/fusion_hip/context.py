@@ -421,6 +421,15 @@ class Context:
         check(self._lib, self._lib.fz_sign_records_async(self._h, c_void_p(d_key_bytes), key_bound, c_void_p(d_c_hat), n, l, bound,
                                                          c_void_p(d_bytes), c_void_p(d_status)))
 
+    def keygen_records_async_dev(self, d_A, d_coef, coef_rows, n, l, key_bound, d_bytes, d_vk, d_status):
+        """key generation straight to the keys' bytes: d_coef holds the secret polynomials, [n][2][d] with coef_rows = 1 (one per
+        (key, half) for all l rows) or [n][2][l][d] with coef_rows = l; record i of d_bytes = the "secret" record of key i, the
+        fields cent(coef mod q) + key_bound, exactly what keygen_core[_bcast]_dev followed by encode_records_async_dev(rows = 2 l,
+        coef) leaves, without the int32 rows; d_vk [n][2][d] as keygen_core_dev writes it, for every key; codes (0, 4) to d_status
+        [n], a refused record's bytes zero (asynchronous)"""
+        check(self._lib, self._lib.fz_keygen_records_async(self._h, c_void_p(d_A), c_void_p(d_coef), coef_rows, n, l, key_bound,
+                                                           c_void_p(d_bytes), c_void_p(d_vk), c_void_p(d_status)))
+
     def decode_records_async_dev(self, d_bytes, n, rows, coef, bound, d_rows, d_status):
         """... and back: codes (0, 6) to d_status [n], a refused record's rows zero (asynchronous)"""
         check(self._lib, self._lib.fz_decode_records_async(self._h, c_void_p(d_bytes), n, rows, 1 if coef else 0, bound,
@@ -611,6 +620,29 @@ class Context:
             raise FusionHipError(FZ_E_BADARG, f"{key.size} bytes of {key.dtype}: {batch} uint8 records of {kb} bytes expected")
         return self._sign_bytes(c, l, bound, lambda s: s.own(DeviceBuffer.from_numpy(self, key.reshape(batch, kb))),
                                 lambda dK, dC, dB, dV: self.sign_records_async_dev(dK, int(key_bound), dC, batch, l, int(bound), dB, dV))
+
+    def keygen_records(self, A, coef, key_bound):
+        """A [l][d]; coef [batch][2][d] (one secret polynomial per (key, half), standing for all l rows) or [batch][2][l][d], the
+        form taken from the shape -> (records uint8 [batch][2 * l * d * wk / 8], vk int32 [batch][2][d], codes int32 [batch]):
+        the "secret" records of keygen_core[_bcast]'s keys under key_bound and their verification keys in one pass
+        (keygen_records_async_dev), codes 0 or 4."""
+        A, coef = _as_i32(A), _as_i32(coef)
+        if A.ndim != 2:
+            raise FusionHipError(FZ_E_BADARG, f"A of shape {A.shape}: [l][d] expected")
+        l, d = A.shape
+        if coef.ndim == 3 and coef.shape[1:] == (2, d):
+            coef_rows = 1
+        elif coef.ndim == 4 and coef.shape[1:] == (2, l, d):
+            coef_rows = l
+        else:
+            raise FusionHipError(FZ_E_BADARG, f"coef of shape {coef.shape}: [batch][2][{d}] or [batch][2][{l}][{d}] expected")
+        batch = coef.shape[0]
+        kb = 2 * l * d * (2 * int(key_bound)).bit_length() // 8
+        with DeviceScope() as s:
+            dA, dC = self._staged(s, [A, coef])
+            dB, dK, dV = self._scratch(s, max(1, batch * kb)), self._scratch(s, max(1, batch * 2 * d * 4)), self._scratch(s, max(1, batch * 4))
+            self.keygen_records_async_dev(dA.ptr, dC.ptr, coef_rows, batch, l, int(key_bound), dB.ptr, dK.ptr, dV.ptr)
+            return dB.to_numpy(np.uint8, (batch, kb)), dK.to_numpy(np.int32, (batch, 2, d)), dV.to_numpy(np.int32, (batch,))
 
     def _sign_bytes(self, c, l, bound, key_dev, launch):
         """the tail sign_encoded and sign_records share, c = c_hat [batch][d]: in one DeviceScope the key (key_dev(scope)) and the

@@ -192,6 +192,12 @@ class BatchScheme:
         MT19937 `random` -- on the device (self.device_sampler) or in C on the host (hostpipe.sample_secret_polys); both
         are pinned against `random` in the tests.
         Unlike the reference this does not leave the process-global `random` generator re-seeded."""
+        with DeviceScope() as s:
+            return self._keygen_from_polys(s, self._sample_polys(s, seeds), device, keep_vk)
+
+    def _sample_polys(self, s, seeds):
+        """the secret polynomials [N][2][d] of `seeds`, by the sampler keygen_batch and keygen_batch_encoded share: a host array,
+        or a DeviceArray owned by the scope `s` when the device sampler made them"""
         p = self.params
         # random.seed(int) uses abs(seed), so negative seeds are legal in the reference; the C / device samplers take the
         # non-negative seeds below 2^64 - 1
@@ -200,46 +206,53 @@ class BatchScheme:
         # the reference's sampler yields ONE polynomial per (key, half) for all l rows (same seed for every matrix
         # entry): 2 KiB per key instead of 166 KiB.  Sampled on the device (an exact MT19937 per lane, fz_sample.hip) when
         # the parameter set allows (weight bound = degree), else by the C clone on the host threads and uploaded.
-        with DeviceScope() as s:
-            polys = None
-            if sd is None:
-                polys = self._python_sampler(seeds)
-            elif self.device_sampler:
-                polys = self._new(s, (sd.size, 2, self.d))
-                try:
-                    self.ctx.sample_secret_polys_dev(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, polys.ptr)
-                except FusionHipError as e:
-                    if e.code != FZ_E_UNSUPPORTED:
-                        raise
-                    self.device_sampler, polys = False, None
-            if polys is None:
-                polys = hostpipe.sample_secret_polys(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, self.threads)   # [N][2][d]
-            return self._keygen_from_polys(s, polys, device, keep_vk)
+        polys = None
+        if sd is None:
+            polys = self._python_sampler(seeds)
+        elif self.device_sampler:
+            polys = self._new(s, (sd.size, 2, self.d))
+            try:
+                self.ctx.sample_secret_polys_dev(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, polys.ptr)
+            except FusionHipError as e:
+                if e.code != FZ_E_UNSUPPORTED:
+                    raise
+                self.device_sampler, polys = False, None
+        if polys is None:
+            polys = hostpipe.sample_secret_polys(sd, p.modulus, p.degree, p.beta_sk, p.omega_sk, self.threads)   # [N][2][d]
+        return polys
 
-    def keygen_batch_encoded(self, seeds, device=False):
+    def keygen_batch_encoded(self, seeds, device=False, keep_vk=False):
         """keygen_batch straight to "secret" records: -> (records uint8 [N][encoded_size(params,
         "secret")], vk [N][2][d]); record i is bit for bit encode("secret", keygen_batch(seeds)[0])[0][i] (an honest key is
-        within beta_sk: the codes are all 0, anything else raises FusionHipError).  With device=True the records stay on the
-        device as a uint8 DeviceArray, which sign_batch_records takes as it is.  Deliberately thin: the existing keygen with
-        sk_hat kept on the device, then the encoder on it inside the same scope -- the int32 key is freed on the way out and
-        never downloaded.
+        within beta_sk: the codes are all 0, anything else raises FusionHipError(FZ_E_BADARG) that names the key).  With
+        device=True the records stay on the device as a uint8 DeviceArray, which sign_batch_records takes as it is; with
+        keep_vk=True a third value is returned, the verification keys as a DeviceArray [N][2][d], as keygen_batch does: pass it
+        as `vk` to sign_batch_records and the keys are not uploaded again.  keygen_batch's sampler (the device sampler, its
+        host clone, or the Python sampler for seeds the clones do not take), then ONE fused pass
+        (keygen_records_async_dev, one polynomial per key half) that range-checks and packs the polynomials as it reads them
+        and transforms them for the verification key alone: the int32 key [N][2][l][d] -- 4.57 times the record -- never
+        exists on the device, and nothing is transformed back.
         Seeds that are not a flat sequence of integers raise FusionHipError(FZ_E_BADARG) before the device is touched.  No
-        seeds: empty numpy arrays for either value of `device` (as sign_batch_records: a DeviceArray would need a device)."""
-        nrows, coef, bound, _, rb = _encoding(self.params, "secret")
+        seeds: empty numpy arrays for either value of `device` (as sign_batch_records: a DeviceArray would need a device),
+        the third value of keep_vk=True included."""
+        _, _, bound, _, rb = _encoding(self.params, "secret")
         seeds = _integer_seeds(seeds)
         n = len(seeds)
         if n == 0:
-            return np.zeros((0, rb), dtype=np.uint8), np.zeros((0, 2, self.d), dtype=np.int32)
+            empty = np.zeros((0, rb), dtype=np.uint8), np.zeros((0, 2, self.d), dtype=np.int32)
+            return empty + (np.zeros((0, 2, self.d), dtype=np.int32),) if keep_vk else empty
         with DeviceScope() as s:
-            dK, vk = self.keygen_batch(seeds, device=True)
-            s.own(dK)
-            dB, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
-            self.ctx.encode_records_async_dev(dK.ptr, n, nrows, coef, bound, dB.ptr, dV.ptr)
+            coef = self._take(s, self._sample_polys(s, seeds), (n, 2, self.d))
+            dA = self._A_dev()
+            dB, dK, dV = self._new(s, (n, rb), np.uint8), self._new(s, (n, 2, self.d)), self._new(s, (n,))
+            self.ctx.keygen_records_async_dev(dA.ptr, coef.ptr, 1, n, self.l, bound, dB.ptr, dK.ptr, dV.ptr)
             codes = dV.numpy()
             if codes.any():
                 bad = int(np.flatnonzero(codes)[0])
                 raise FusionHipError(FZ_E_BADARG, f"key {bad}: {ENCODING_REASONS[int(codes[bad])]}")
-            return (s.release(dB) if device else dB.numpy()), vk
+            vk = dK.numpy()
+            recs = s.release(dB) if device else dB.numpy()
+            return (recs, vk, s.release(dK)) if keep_vk else (recs, vk)
 
     def _python_sampler(self, seeds):
         """the secret polynomials [N][2][d] for seeds the C / device MT19937 clones do not take (negative seeds, where seed + 1

@@ -363,6 +363,26 @@ FZ_API int fz_sign_encoded_async(fz_ctx *ctx, const int32_t *d_sk_hat, const int
 FZ_API int fz_sign_records_async(fz_ctx *ctx, const uint8_t *d_key_bytes, int64_t key_bound, const int32_t *d_c_hat, size_t N, int l,
                                  int64_t bound, uint8_t *d_bytes, int *d_status);
 
+/* key generation straight to the keys' bytes (fusion/fusion.py:338-373 and the encoding of the signing key in one pass; no int32
+ * row of the key reaches memory).  d_A [l][degree] is the public challenge, any int32.  d_coef holds the secret polynomials in
+ * the coefficient domain, any int32: with coef_rows == 1 [N][2][degree], one polynomial per (key, half) standing for all l rows
+ * (what fz_keygen_core_bcast reads and fz_sample_secret_polys_dev writes); with coef_rows == l [N][2][l][degree], as
+ * fz_keygen_core reads it.  With s = cent(coef mod q) and wk = bit_length(2 * key_bound), record i of d_key_bytes
+ * [N][2 * l * degree * wk / 8] is the "secret" record of key i in the format of fz_encode_records_async: the fields
+ * s + key_bound, row-major over [2][l][degree], left half first, LSB first (coef_rows == 1: the one polynomial repeated for
+ * the l rows).  d_status[i] = FZ_VERDICT_NORM when some |s| of key i is above key_bound, else 0; a refused record is all zero
+ * bytes, the others are unaffected.  d_vk [N][2][degree] is bit for bit what fz_keygen_core / fz_keygen_core_bcast writes for
+ * the same d_A and d_coef, for EVERY key whatever its status.  On a context whose tables are a root's, records and status are
+ * exactly what fz_keygen_core[_bcast] followed by fz_encode_records_async(rows = 2 l, coef = 1, key_bound) leaves; on a context
+ * created with fz_ctx_create_tables the definition above holds (the fields straight from the coefficients, vk by the context's
+ * forward tables).  The inputs are not written.  Rules of fz_sign_records_async, in its order: FZ_E_BADARG for a NULL context,
+ * l < 1, coef_rows other than 1 or l, or key_bound outside [1, (q-1)/2]; N == 0 does nothing and writes nothing; FZ_E_BADARG for
+ * a pointer that is NULL or not 16-byte aligned (all five); FZ_E_UNSUPPORTED for degrees other than 64 and 256.  Asynchronous on
+ * the context's stream, allocation-free, capturable by fz_graph_* (the clear of d_status and the zeroing of refused records are
+ * part of the captured work). */
+FZ_API int fz_keygen_records_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int coef_rows, size_t N, int l,
+                                   int64_t key_bound, uint8_t *d_key_bytes, int32_t *d_vk, int *d_status);
+
 /* the range check of fz_decode_records_async alone (no transform, no rows): status per record 0 or FZ_VERDICT_ENCODING (a field
  * > 2 * bound); nothing else is written.  Same arguments and rules as fz_decode_records_async, for either kind of record. */
 FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status);
