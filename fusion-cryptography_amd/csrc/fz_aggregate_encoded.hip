@@ -74,16 +74,13 @@ int launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *a
 
 }  // namespace
 
-// resident grids of the two kernels this context launches (context creation; degrees 64 / 256, nothing to query at the others),
-// then what the other consumer of the bytes needs from context creation (fz_verify_encoded.hip), as fz_ntt_query_grid goes on to
-// fz_records_query_grid
+// resident grids of the two kernels this context launches (context creation; degrees 64 / 256, nothing to query at the others)
 int fz_aggregate_encoded_query_grid(fz_ctx *ctx) {
-    const int rc = fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
+    return fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
         const int rc = fz_resident_grid(ctx, aggregate_encoded<logd(), fast()>, 64 * kWavesPerBlock, "occupancy query (aggregate_encoded)",
                                         &ctx->grid_aggenc);
         return rc != FZ_OK ? rc : fz_resident_grid(ctx, encoded_check, 64 * kWavesPerBlock, "occupancy query (encoded_check)", &ctx->grid_check);
     });
-    return rc != FZ_OK ? rc : fz_verify_encoded_setup(ctx);
 }
 
 // fz_check_records_async: d_status cleared, then the range check over the byte stream (asynchronous, allocation-free)

@@ -79,11 +79,10 @@ int launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int
 
 // the kernel's own resident grid (context creation; degrees 64 / 256, nothing to query at the others)
 int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx) {
-    const int rc = fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
+    return fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
         return fz_resident_grid(ctx, aggregate_encoded_ragged<logd(), fast()>, 64 * kWavesPerBlock,
                                 "occupancy query (aggregate_encoded_ragged)", &ctx->grid_aggenc_rag);
     });
-    return rc != FZ_OK ? rc : fz_sign_records_query_grid(ctx);       // then what signing from records needs (fz_sign_records.hip)
 }
 
 // fz_aggregate_encoded_ragged_async: the partials zeroed (theirs alone: the words between two partials are not touched), the fused

@@ -1,5 +1,6 @@
 // fz_capi.hip -- the C ABI of libfusion_hip.so (include/fusion_hip.h): the thin wrappers that check arguments and enqueue the
-// transform, pointwise and scheme kernels, and the host side of the device challenge pipeline and the device sampler.
+// transform, pointwise and scheme kernels, and the host side of the device challenge pipeline and the device sampler.  (The
+// compact-bytes entries: fz_records_capi.hip.)
 #include "fz_internal.h"
 #include "../../include/fusion_hip.h"
 #include "../../include/fusion_hip_diag.h"
@@ -385,159 +386,6 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
         return fz_set_error(FZ_E_UNSUPPORTED, "per-signature verification needs the fused kernel (degree 64 or 256)");
     FZ_DEV(ctx);
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
-}
-
-// a bound B of some kind of record, `what` for the message: B in [1, (q-1)/2] -> *w = bit_length(2 B), the kind's field width
-static int records_bound(const fz_ctx *ctx, int64_t bound, const char *what, int *w) {
-    FZ_REQUIRE(bound >= 1 && bound <= ((int64_t)ctx->q - 1) / 2, "%s %lld outside [1, (q-1)/2]", what, (long long)bound);
-    int b = 0;
-    while ((2 * bound) >> b) ++b;
-    *w = b;
-    return FZ_OK;
-}
-
-// compact byte encoding: the checks of all seven entries, in the order that decides the return code when more than one thing is
-// wrong: context, rows and bound; n == 0 is FZ_OK from here on; the entry's pointers (`ptrs_wrong`: what is wrong with them, NULL
-// when nothing is -- which pointers an entry takes and how they must be aligned is its own business); degree; size.
-// -> *w = the field width (records_bound).  Conditions of an entry that hold whatever n is come before this call, its own limits after it.
-static int records_args(fz_ctx *ctx, size_t n, int rows, int64_t bound, const char *ptrs_wrong, int *w) {
-    FZ_REQUIRE(ctx && rows >= 1, "bad argument");
-    FZ_TRY(records_bound(ctx, bound, "bound", w));
-    if (n == 0) return FZ_OK;
-    FZ_REQUIRE(!ptrs_wrong, "%s", ptrs_wrong);
-    if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
-    FZ_REQUIRE((uint64_t)rows * (uint64_t)ctx->degree <= 0x7fffffffull && n <= ((size_t)-1 >> 3) / ((size_t)rows * ctx->degree),
-               "%zu records of %d rows are too many", n, rows);
-    return FZ_OK;
-}
-
-// the three buffers of an entry that wants all of them 16-byte aligned
-static const char *records_ptrs(const void *a, const void *b, const void *c) {
-    if (!a || !b || !c) return "NULL argument";
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) != 0 ? "buffers must be 16-byte aligned" : nullptr;
-}
-
-// the consumers that walk ONE record's chunks (blockIdx names the record): every record must begin on a 16-byte unit
-static int records_whole_units(const fz_ctx *ctx, int rows, int w) {
-    const size_t rb = fz_record_bytes(ctx->degree, rows, w);
-    if (rb % 16 != 0) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: reading them record by record needs a multiple of 16", rb);
-    return FZ_OK;
-}
-
-int fz_encode_records_async(fz_ctx *ctx, const int32_t *d_rows, size_t n, int rows, int coef, int64_t bound, uint8_t *d_bytes,
-                            int *d_status) {
-    int w = 0;
-    FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_rows, d_bytes, d_status), &w));
-    if (n == 0) return FZ_OK;
-    FZ_DEV(ctx);
-    return fz_launch_records(ctx, false, d_rows, d_bytes, n, rows, coef != 0, w, bound, d_status);
-}
-
-int fz_decode_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int coef, int64_t bound, int32_t *d_rows,
-                            int *d_status) {
-    int w = 0;
-    FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_bytes, d_rows, d_status), &w));
-    if (n == 0) return FZ_OK;
-    FZ_DEV(ctx);
-    return fz_launch_records(ctx, true, d_bytes, d_rows, n, rows, coef != 0, w, bound, d_status);
-}
-
-// sigma = left_sk_hat * c_hat + right_sk_hat (fusion/fusion.py:534-557) and its encoding in one pass: the signature's rows never
-// reach memory
-int fz_sign_encoded_async(fz_ctx *ctx, const int32_t *d_sk_hat, const int32_t *d_c_hat, size_t N, int l, int64_t bound, uint8_t *d_bytes,
-                          int *d_status) {
-    int w = 0;
-    const char *ptrs_wrong = records_ptrs(d_sk_hat, d_bytes, d_status);
-    if (!ptrs_wrong) ptrs_wrong = records_ptrs(d_c_hat, d_c_hat, d_c_hat);
-    FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
-    if (N == 0) return FZ_OK;
-    FZ_DEV(ctx);
-    return fz_launch_sign_encoded(ctx, d_sk_hat, d_c_hat, N, l, w, bound, d_bytes, d_status);
-}
-
-// the same from the key's "secret" record: z = INTT(NTT(sL) * c_hat) + sR, the right half added in the coefficient domain
-// (fusion/fusion.py:534-557 by linearity), and its encoding in one pass: neither the key's nor the signature's rows reach memory.
-// fz_sign_encoded_async's checks in its order; the key's bound is held to the output bound's range
-int fz_sign_records_async(fz_ctx *ctx, const uint8_t *d_key_bytes, int64_t key_bound, const int32_t *d_c_hat, size_t N, int l,
-                          int64_t bound, uint8_t *d_bytes, int *d_status) {
-    int w = 0, wk = 0;
-    const char *ptrs_wrong = records_ptrs(d_key_bytes, d_bytes, d_status);
-    if (!ptrs_wrong) ptrs_wrong = records_ptrs(d_c_hat, d_c_hat, d_c_hat);
-    FZ_REQUIRE(ctx && l >= 1, "bad argument");
-    FZ_TRY(records_bound(ctx, key_bound, "key bound", &wk));
-    FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
-    if (N == 0) return FZ_OK;
-    FZ_DEV(ctx);
-    return fz_launch_sign_records(ctx, d_key_bytes, wk, key_bound, d_c_hat, N, l, w, bound, d_bytes, d_status);
-}
-
-int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status) {
-    int w = 0;
-    FZ_TRY(records_args(ctx, n, rows, bound, records_ptrs(d_bytes, d_bytes, d_status), &w));
-    if (n == 0) return FZ_OK;
-    FZ_DEV(ctx);
-    return fz_launch_check_records(ctx, d_bytes, n, rows, w, bound, d_status);
-}
-
-int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip, size_t N, int l,
-                               int64_t bound, int64_t *d_partial, int32_t *d_out) {
-    int w = 0;
-    FZ_REQUIRE(N == 0 || d_alpha_hat, "NULL argument");
-    FZ_REQUIRE((((uintptr_t)d_alpha_hat | (uintptr_t)d_out) & 15) == 0, "alpha_hat and the aggregate must be 16-byte aligned");
-    FZ_TRY(records_args(ctx, N, l, bound, records_ptrs(d_bytes, d_partial, d_alpha_hat), &w));
-    if (N == 0) return FZ_OK;
-    FZ_TRY(records_whole_units(ctx, l, w));
-    if (N >= ((size_t)1 << 22))
-        return fz_set_error(FZ_E_UNSUPPORTED, "N=%zu too large for exact fp64 accumulation (< 2^22)", N);
-    FZ_DEV(ctx);
-    return fz_launch_aggregate_encoded(ctx, d_bytes, d_alpha_hat, d_skip, N, l, w, bound, d_partial, d_out);
-}
-
-// many committees in one launch: group g owns records [h_offsets[g], h_offsets[g + 1]).  The argument rules are
-// fz_aggregate_encoded_async's, in its order, then the offsets and the stride.
-int fz_aggregate_encoded_ragged_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
-                                      const size_t *h_offsets, size_t groups, int l, int64_t bound, int64_t *d_partial,
-                                      size_t partial_stride, int32_t *d_out) {
-    int w = 0;
-    FZ_REQUIRE(groups == 0 || h_offsets, "NULL argument");
-    const size_t total = groups ? h_offsets[groups] : 0;
-    FZ_REQUIRE(total == 0 || d_alpha_hat, "NULL argument");
-    FZ_REQUIRE((((uintptr_t)d_alpha_hat | (uintptr_t)d_out) & 15) == 0, "alpha_hat and the aggregates must be 16-byte aligned");
-    // (a call whose groups are all empty reads no byte: the stream may be NULL then)
-    FZ_TRY(records_args(ctx, groups == 0 ? 0 : (total ? total : 1), l, bound, records_ptrs(total ? (const void *)d_bytes : (const void *)d_partial, d_partial,
-                                                           total ? (const void *)d_alpha_hat : (const void *)d_partial), &w));
-    if (groups == 0) return FZ_OK;
-    FZ_TRY(records_whole_units(ctx, l, w));
-    for (size_t g = 0; g < groups; ++g) FZ_REQUIRE(h_offsets[g] <= h_offsets[g + 1], "offsets must not decrease");
-    FZ_REQUIRE(groups == 1 || (partial_stride >= (size_t)l * ctx->degree && (partial_stride & 1) == 0),
-               "partial_stride must be at least l * degree, and even (16-byte aligned partials)");
-    for (size_t g = 0; g < groups; ++g)
-        if (h_offsets[g + 1] - h_offsets[g] >= ((size_t)1 << 22))
-            return fz_set_error(FZ_E_UNSUPPORTED, "group %zu: %zu signers are too many for exact fp64 accumulation (< 2^22)", g,
-                                h_offsets[g + 1] - h_offsets[g]);
-    if (total >= 0xffffffc0ull) return fz_set_error(FZ_E_UNSUPPORTED, "%zu records in one call: signer indices are 32-bit", total);
-    FZ_DEV(ctx);
-    return fz_launch_aggregate_encoded_ragged(ctx, d_bytes, d_alpha_hat, d_skip, h_offsets, groups, l, w, bound, d_partial, partial_stride,
-                                              d_out);
-}
-
-int fz_verify_encoded_async(fz_ctx *ctx, const int32_t *d_A, const uint8_t *d_bytes, size_t N, int l, int64_t bound,
-                            const int32_t *d_target, const int32_t *d_vk, const int32_t *d_c_hat, int *d_verdicts) {
-    int w = 0;
-    FZ_REQUIRE((d_target != nullptr) != (d_vk != nullptr || d_c_hat != nullptr) && (d_vk != nullptr) == (d_c_hat != nullptr),
-               "exactly one of d_target, or the pair d_vk and d_c_hat, must be given");
-    const char *ptrs_wrong = nullptr;
-    if (!d_A || !d_bytes || !d_verdicts) ptrs_wrong = "NULL argument";
-    else if ((((uintptr_t)d_bytes | (uintptr_t)d_A) & 15) != 0) ptrs_wrong = "the bytes and A must be 16-byte aligned";
-    else if ((((uintptr_t)d_target | (uintptr_t)d_vk | (uintptr_t)d_c_hat | (uintptr_t)d_verdicts) & 3) != 0)
-        ptrs_wrong = "target, keys, challenges and verdicts must be 4-byte aligned";
-    FZ_TRY(records_args(ctx, N, l, bound, ptrs_wrong, &w));
-    if (N == 0) return FZ_OK;
-    FZ_TRY(records_whole_units(ctx, l, w));
-    const size_t rb = fz_record_bytes(ctx->degree, l, w);
-    if (rb > 0xffffffffull) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes are too long", rb);
-    FZ_DEV(ctx);
-    return fz_launch_verify_encoded(ctx, d_A, d_bytes, N, l, w, bound, d_target, d_vk, d_c_hat, d_verdicts);
 }
 
 int fz_verify_partials_batch_async(fz_ctx *ctx, const int32_t *d_A, const int64_t *d_partial, size_t partial_stride,

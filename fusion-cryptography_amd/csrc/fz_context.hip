@@ -154,6 +154,12 @@ static int upload_doubles(const double *h, size_t n, double **d_out) {
     return FZ_OK;
 }
 
+// what the kernel units need from context creation (fz_internal.h), in the order it runs them
+static int (*const kUnitSetup[])(fz_ctx *) = {
+    fz_ntt_query_grid,           fz_records_query_grid,                fz_aggregate_encoded_query_grid, fz_verify_encoded_setup,
+    fz_sign_encoded_query_grid,  fz_aggregate_many_encoded_query_grid, fz_sign_records_query_grid,      fz_keygen_records_query_grid,
+};
+
 // h_fwd / h_inv != NULL: the context's twiddle tables are THESE (fz_ctx_create_tables) instead of the bit-reversed powers of a root
 static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint32_t inv_root, const uint32_t *h_fwd, const uint32_t *h_inv,
                       fz_ctx **out) {
@@ -322,8 +328,8 @@ static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint
     }
     int *d_verdict = nullptr;
     if (rc == FZ_OK) rc = fz_verdict_area(c, 64, &d_verdict);
-    if (rc == FZ_OK && !ring_only) rc = fz_ntt_query_grid(c);
-    if (rc == FZ_OK && !ring_only) rc = fz_aggregate_encoded_query_grid(c);
+    for (const auto setup : kUnitSetup)
+        if (rc == FZ_OK && !ring_only) rc = setup(c);
     free(tw); free(itw); free(twB); free(itwB); free(pairs);
     if (rc != FZ_OK) { fz_ctx_destroy(c); return rc; }
     fz_registry_add(c);

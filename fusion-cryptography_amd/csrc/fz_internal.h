@@ -255,9 +255,20 @@ int fz_resident_grid(const fz_ctx *ctx, K kernel, int threads, const char *what,
     return rc;
 }
 
+// What each kernel unit needs from context creation, which runs them in this order for every context with transforms (fz_context.hip)
+// and stops at the first error: the resident grid of each persistent kernel (ctx->grid_*; degrees 64 / 256 -- the transforms' 32
+// to 256 -- and nothing to query at the others) and the one allocation, ctx->d_venc.  Each does its own unit's work alone.
+int fz_ntt_query_grid(fz_ctx *ctx);                     // grid_fwd, grid_inv (fz_ntt.hip)
+int fz_records_query_grid(fz_ctx *ctx);                 // grid_rec (fz_records.hip)
+int fz_aggregate_encoded_query_grid(fz_ctx *ctx);       // grid_aggenc, grid_check (fz_aggregate_encoded.hip)
+int fz_verify_encoded_setup(fz_ctx *ctx);               // d_venc, venc_bytes (fz_verify_encoded.hip)
+int fz_sign_encoded_query_grid(fz_ctx *ctx);            // grid_signenc (fz_sign_encoded.hip)
+int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx);  // grid_aggenc_rag (fz_aggregate_many_encoded.hip)
+int fz_sign_records_query_grid(fz_ctx *ctx);            // grid_signrec (fz_sign_records.hip)
+int fz_keygen_records_query_grid(fz_ctx *ctx);          // grid_keyrec (fz_keygen_records.hip)
+
 // transforms (fz_ntt.hip)
 int fz_launch_ntt(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch, bool inverse);
-int fz_ntt_query_grid(fz_ctx *ctx);                                // resident grids of the 16-per-lane transforms and of the records kernels
 int fz_launch_ntt_multi(fz_ctx *ctx, FzMultiJobs &jobs);           // degree 64 / 256; the radix-4 path fills jobs.end
 // the layout of a 16-per-lane multi-job launch: order[k] = the table entry that runs k-th (the first *consumers of them read what
 // `prev` wrote), end[k] = workgroups up to and including it, for `resident` workgroups on the chip at once, *keep = the direction
@@ -277,7 +288,6 @@ bool fz_polymul16_ok(const fz_ctx *ctx, const int32_t *f, const int32_t *g, cons
 static inline size_t fz_record_bytes(int degree, int rows, int w) { return (size_t)rows * (size_t)degree / 8 * (size_t)w; }
 int fz_launch_records(fz_ctx *ctx, bool decode, const void *src, void *dst, size_t n, int rows, bool coef, int w, int64_t bound,
                       int *d_status);
-int fz_records_query_grid(fz_ctx *ctx);                            // ctx->grid_rec (fz_ntt_query_grid calls it)
 // the follow-up of every launch that leaves records and status words: record i of `dst` (rec_bytes each, a multiple of 8) is
 // zeroed where d_status[i] != 0
 int fz_launch_records_zero(fz_ctx *ctx, const int *d_status, size_t n, void *dst, size_t rec_bytes);
@@ -297,14 +307,12 @@ int fz_records_pass(fz_ctx *ctx, int *d_status, size_t n, const char *what, F &&
 // signing straight to the bytes (fz_sign_encoded.hip; degree 64 / 256): record i of d_bytes = the encoding of
 // cent(cent(L_i (.) c_i) + R_i) from sk_hat [n][2][l][degree] and c_hat [n][degree], any int32; d_status [n] cleared, then 0 or
 // FZ_VERDICT_NORM; refused records zeroed
-int fz_sign_encoded_query_grid(fz_ctx *ctx);                       // ctx->grid_signenc, then fz_aggregate_many_encoded_query_grid (context creation: fz_verify_encoded_setup calls it)
 int fz_launch_sign_encoded(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat, size_t n, int l, int w, int64_t bound,
                            uint8_t *d_bytes, int *d_status);
 
 // signing straight from "secret" records to the bytes (fz_sign_records.hip; degree 64 / 256): record i of d_bytes = the encoding of
 // cent(INV(cent(FWD(sL_i) (.) c_i)) + sR_i) from key records [n][2][l][degree] of wk-bit fields s + key_bound and c_hat [n][degree], any
 // int32; d_status [n] cleared, then 0, FZ_VERDICT_NORM or FZ_VERDICT_ENCODING (a key field above 2 key_bound); refused records zeroed
-int fz_sign_records_query_grid(fz_ctx *ctx);                       // ctx->grid_signrec, then fz_keygen_records_query_grid (context creation: fz_aggregate_many_encoded_query_grid calls it)
 int fz_launch_sign_records(fz_ctx *ctx, const uint8_t *key_bytes, int wk, int64_t key_bound, const int32_t *c_hat, size_t n, int l,
                            int w, int64_t bound, uint8_t *d_bytes, int *d_status);
 
@@ -312,7 +320,6 @@ int fz_launch_sign_records(fz_ctx *ctx, const uint8_t *key_bytes, int wk, int64_
 // (wk bits) of s = cent(coef mod q) over [2][l][degree], from coef [n][2][degree] (one polynomial per half for all l rows) or,
 // with `rows`, [n][2][l][degree]; d_vk [n][2][degree] as fz_launch_keygen_fused writes it; d_status [n] cleared, then 0 or
 // FZ_VERDICT_NORM; refused records zeroed
-int fz_keygen_records_query_grid(fz_ctx *ctx);                     // ctx->grid_keyrec (context creation: fz_sign_records_query_grid calls it)
 int fz_launch_keygen_records(fz_ctx *ctx, const int32_t *A, const int32_t *coef, bool rows, size_t n, int l, int wk, int64_t key_bound,
                              uint8_t *d_bytes, int32_t *d_vk, int *d_status);
 
@@ -320,7 +327,6 @@ int fz_launch_keygen_records(fz_ctx *ctx, const int32_t *A, const int32_t *coef,
 // (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from
 // their bytes: d_partial [l][degree] int64 zeroed, then sum_i cent(NTT(z_i) (.) alpha_hat_i) over the signers with skip[i] == 0
 // (skip NULL: all), d_out = cent(d_partial) when not NULL.  Records of the aggregation are multiples of 16 bytes.
-int fz_aggregate_encoded_query_grid(fz_ctx *ctx);                  // ctx->grid_aggenc, ctx->grid_check, then fz_verify_encoded_setup (context creation)
 int fz_launch_check_records(fz_ctx *ctx, const uint8_t *bytes, size_t n, int rows, int w, int64_t bound, int *d_status);
 int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, size_t n, int l, int w,
                                 int64_t bound, int64_t *d_partial, int32_t *d_out);
@@ -329,14 +335,12 @@ int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t
 // of `groups` owns records [h_offsets[g], h_offsets[g + 1]) of the concatenated byte stream and the same rows of alpha and skip;
 // its int64 partial [l][degree] at d_partial + g * pstride is zeroed, then summed as fz_launch_aggregate_encoded does; d_out
 // [groups][l][degree] = cent(partial) when not NULL.  h_offsets is read before the call returns.
-int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx);             // ctx->grid_aggenc_rag, then fz_sign_records_query_grid (context creation: fz_sign_encoded_query_grid calls it)
 int fz_launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const size_t *h_offsets,
                                        size_t groups, int l, int w, int64_t bound, int64_t *d_partial, size_t pstride, int32_t *d_out);
 
 // verification straight from the bytes (fz_verify_encoded.hip; degree 64 / 256): d_verdict [N] = 0, FZ_VERDICT_TARGET_MISMATCH or
 // FZ_VERDICT_ENCODING of N records of l rows against `target` [N][degree] (any residues) or, when vk != NULL, against
 // cent(vkL (.) c + vkR) from vk [N][2][degree] and chal [N][degree].  Records are multiples of 16 bytes.
-int fz_verify_encoded_setup(fz_ctx *ctx);                          // ctx->d_venc, then fz_sign_encoded_query_grid (context creation: fz_aggregate_encoded_query_grid calls it)
 int fz_launch_verify_encoded(fz_ctx *ctx, const int32_t *A, const uint8_t *bytes, size_t N, int l, int w, int64_t bound,
                              const int32_t *target, const int32_t *vk, const int32_t *chal, int *d_verdict);
 

@@ -2,8 +2,8 @@
 // are range-checked and packed as they are read, their transform serves the verification key alone, and no int32 row of the
 // key ever reaches memory.  keygen_records_bcast (one polynomial per (key, half), the scheme's seeded keys: a resident grid
 // that sums A once per workgroup and then walks the (key, half) units) and keygen_records_rows (l polynomials per (key, half):
-// keygen_fused with the row's fields packed instead of its transform stored); their launchers, the resident-grid query and
-// the entry fz_keygen_records_async.  Both kernels stand on the radix-4 structure of keygen_bcast_fused / keygen_fused
+// keygen_fused with the row's fields packed instead of its transform stored); their launcher and the resident-grid query
+// (the entry fz_keygen_records_async: fz_records_capi.hip).  Both kernels stand on the radix-4 structure of keygen_bcast_fused / keygen_fused
 // (fz_scheme_fused.hip) and take its LDS: a 2 KiB transform region per wave and 8 KiB where the workgroup's waves meet.
 #include "fz_records_dev.h"
 #include "../../include/fusion_hip.h"
@@ -242,13 +242,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void keygen_records_rows(const
     }
 }
 
-// field width of a bound in [1, (q-1)/2]
-int key_width(int64_t bound) {
-    int b = 0;
-    while ((2 * bound) >> b) ++b;
-    return b;
-}
-
 }  // namespace
 
 // the seeded kernel's own resident grid (context creation; degrees 64 / 256, nothing to query at the others)
@@ -281,24 +274,4 @@ int fz_launch_keygen_records(fz_ctx *ctx, const int32_t *A, const int32_t *coef,
         });
     };
     return fz_records_pass(ctx, d_status, n, "keygen_records launch", launch, d_bytes, fz_record_bytes(ctx->degree, 2 * l, wk));
-}
-
-// Key generation straight to "secret" records.  fz_sign_records_async's checks in its order: context, l, the form and the bound;
-// N == 0; the five pointers; the degree; the size (a record's values fit 31 bits, the batch's bits a size_t, a workgroup per
-// (key, half) the grid).
-int fz_keygen_records_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int coef_rows, size_t N, int l, int64_t key_bound,
-                            uint8_t *d_key_bytes, int32_t *d_vk, int *d_status) {
-    FZ_REQUIRE(ctx && l >= 1, "bad argument");
-    FZ_REQUIRE(coef_rows == 1 || coef_rows == l, "coef_rows %d: 1 or l = %d", coef_rows, l);
-    FZ_REQUIRE(key_bound >= 1 && key_bound <= ((int64_t)ctx->q - 1) / 2, "key bound %lld outside [1, (q-1)/2]", (long long)key_bound);
-    if (N == 0) return FZ_OK;
-    FZ_REQUIRE(d_A && d_coef && d_key_bytes && d_vk && d_status, "NULL argument");
-    FZ_REQUIRE((((uintptr_t)d_A | (uintptr_t)d_coef | (uintptr_t)d_key_bytes | (uintptr_t)d_vk | (uintptr_t)d_status) & 15) == 0,
-               "buffers must be 16-byte aligned");
-    if (ctx->logd != 6 && ctx->logd != 8) return fz_set_error(FZ_E_UNSUPPORTED, "the byte encoding needs degree 64 or 256");
-    FZ_REQUIRE(2 * (uint64_t)l * (uint64_t)ctx->degree <= 0x7fffffffull && N <= ((size_t)-1 >> 3) / (2 * (size_t)l * ctx->degree) &&
-               N <= 0x3fffffffu, "%zu keys of %d rows are too many", N, l);
-    FZ_DEV(ctx);
-    return fz_launch_keygen_records(ctx, d_A, d_coef, coef_rows == l && l > 1, N, l, key_width(key_bound), key_bound, d_key_bytes, d_vk,
-                                    d_status);
 }

@@ -424,7 +424,7 @@ int fz_ntt_query_grid(fz_ctx *ctx) {
         return rf != FZ_OK ? rf : fz_resident_grid(ctx, ntt_inv16<logd(), fast()>, 64 * kWavesPerBlock, "occupancy query (inv)", &inv);
     });
     if (rc == FZ_OK) { ctx->grid_fwd = fwd; ctx->grid_inv = inv; }       // both or neither
-    return rc == FZ_OK ? fz_records_query_grid(ctx) : rc;      // (the byte encoding: degrees 64 / 256, nothing to query at the others)
+    return rc;
 }
 
 int fz_launch_ntt(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch, bool inverse) {

@@ -215,13 +215,11 @@ void launch_sign_encode(fz_ctx *ctx, const int32_t *sk_hat, const int32_t *c_hat
 
 // the kernel's own resident grid (context creation; degrees 64 / 256, nothing to query at the others): two workgroups per
 // CU (176 - 185 VGPRs) against records_encode's three, whose grid would leave a third of the workgroups for a second round of
-// the walk (see launch_records_k); then what the ragged aggregation needs from context creation (fz_aggregate_many_encoded.hip),
-// as fz_verify_encoded_setup goes on to here
+// the walk (see launch_records_k)
 int fz_sign_encoded_query_grid(fz_ctx *ctx) {
-    const int rc = fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
+    return fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
         return fz_resident_grid(ctx, sign_encode<logd(), fast()>, 64 * kWavesPerBlock, "occupancy query (sign_encode)", &ctx->grid_signenc);
     });
-    return rc != FZ_OK ? rc : fz_aggregate_many_encoded_query_grid(ctx);
 }
 
 // fz_sign_encoded_async: the fused pass over the batch as a fz_records_pass

@@ -255,13 +255,11 @@ void launch_sign_records(fz_ctx *ctx, const uint8_t *key, const int32_t *c_hat, 
 
 }  // namespace
 
-// the kernel's own resident grid (context creation; degrees 64 / 256, nothing to query at the others), then what the producer of
-// the key records needs (fz_keygen_records.hip)
+// the kernel's own resident grid (context creation; degrees 64 / 256, nothing to query at the others)
 int fz_sign_records_query_grid(fz_ctx *ctx) {
-    const int rc = fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
+    return fz_dispatch<6, 8>(ctx, FZ_OK, [&](auto logd, auto fast) {
         return fz_resident_grid(ctx, sign_records<logd(), fast()>, 64 * kWavesPerBlock, "occupancy query (sign_records)", &ctx->grid_signrec);
     });
-    return rc != FZ_OK ? rc : fz_keygen_records_query_grid(ctx);
 }
 
 // fz_sign_records_async: the fused pass over the batch as a fz_records_pass

@@ -172,15 +172,14 @@ __global__ __launch_bounds__(1 << LOGD) void verify_encoded_finish(const unsigne
 }  // namespace
 
 // the shared area of the launches with R > 1, a slot per record: R >= 2 means 2 * records <= 2 * num_cu, so num_cu slots (526 KB
-// on 256 CUs at degree 256).  Allocated once per context, at its creation (degrees 64 / 256; nothing at the others).  Then what
-// the producer of the bytes needs from context creation (fz_sign_encoded.hip), as fz_aggregate_encoded_query_grid goes on to here.
+// on 256 CUs at degree 256).  Allocated once per context, at its creation (degrees 64 / 256; nothing at the others).
 int fz_verify_encoded_setup(fz_ctx *ctx) {
     if (ctx->logd != 6 && ctx->logd != 8) return FZ_OK;
     const size_t bytes = (size_t)ctx->num_cu * ((size_t)ctx->degree + 1) * sizeof(unsigned long long);
     const int rc = fz_check_hip(hipMalloc((void **)&ctx->d_venc, bytes), "verify_encoded area alloc");
     if (rc == FZ_OK) ctx->venc_bytes = bytes;
     else ctx->d_venc = nullptr;
-    return rc != FZ_OK ? rc : fz_sign_encoded_query_grid(ctx);
+    return rc;
 }
 
 // fz_verify_encoded_async: one launch per at most max-grid-y records (blockIdx.y is the record).  R workgroups per record by

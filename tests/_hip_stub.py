@@ -139,9 +139,15 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t st) { rec("hipEventRecord", 
 hipError_t hipEventSynchronize(hipEvent_t e) { rec("hipEventSynchronize", e); return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 1.0f; return hipSuccess; }
 }
-// what fz_context.hip and fz_diag.hip take from the kernel units
+// what fz_context.hip and fz_diag.hip take from the kernel units: the setup of each unit (none is linked), and fz_ntt.hip's helpers
 int fz_ntt_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_records_query_grid(fz_ctx *) { return FZ_OK; }
 int fz_aggregate_encoded_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_verify_encoded_setup(fz_ctx *) { return FZ_OK; }
+int fz_sign_encoded_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_aggregate_many_encoded_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_sign_records_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_keygen_records_query_grid(fz_ctx *) { return FZ_OK; }
 int fz_launch_diag(fz_ctx *, int, const void *, void *, size_t) { return FZ_OK; }
 int fz_launch_diag_clock(hipStream_t, unsigned long long, unsigned long long *) { return FZ_OK; }
 unsigned fz_multi_plan(const FzMultiJobs &, int, const FzProduced *, int, bool, unsigned, int *, unsigned *, int *, int *) { return 0; }

@@ -5,8 +5,8 @@ case's operand is the smallest that crosses its thresholds, with a ragged remain
 changes a SAMPLED row (so the sampled-row check alone sees it; the whole-buffer comparison sees every changed row); the alias rows
 a wrapped store would overwrite are sampled; the pieces of the whole-buffer comparison are out of every model's reach.
 
-Part two: the size refusals of the entry points, on both sides of their limit, without a GPU.  csrc/fz_capi.hip is compiled for
-the host with the REAL host launchers of fz_ntt.hip, fz_pointwise.hip, fz_wide.hip and fz_verify_encoded.hip (their kernel
+Part two: the size refusals of the entry points, on both sides of their limit, without a GPU.  csrc/fz_capi.hip and csrc/fz_records_capi.hip are compiled
+for the host with the REAL host launchers of fz_ntt.hip, fz_pointwise.hip, fz_wide.hip and fz_verify_encoded.hip (their kernel
 launches end in a recording hipLaunchKernel of the stub runtime: kernel name, grid, and the count arguments) and recording
 stand-ins for the other fz_launch_* (they store the counts they were handed), linked with a driver into a stand-alone program
 under AddressSanitizer and UBSan.  At the limit the call reaches the launcher with its counts unchanged; at limit + 1 it
@@ -158,10 +158,10 @@ def test_every_case_has_a_gpu_test():
 
 
 # ---- part two: the size refusals ------------------------------------------------------------------------------------------------------
-UNITS = ("fz_capi", "fz_context", "fz_diag", "fz_ntt", "fz_pointwise", "fz_wide", "fz_verify_encoded")
+UNITS = ("fz_capi", "fz_records_capi", "fz_context", "fz_diag", "fz_ntt", "fz_pointwise", "fz_wide", "fz_verify_encoded")
 MARK = "// what fz_context.hip and fz_diag.hip take from the kernel units"
 assert MARK in STUB
-RUNTIME = STUB.split(MARK)[0]           # (fz_ntt.hip is real here and brings four of the five stand-ins behind the mark itself)
+RUNTIME = STUB.split(MARK)[0]           # (the stand-ins behind the mark are per unit: the driver has its own, for the units not linked here)
 
 DRIVER = RUNTIME + r'''
 #include <map>
@@ -224,6 +224,7 @@ int fz_launch_records(fz_ctx *, bool, const void *, void *, size_t n, int rows, 
 int fz_launch_check_records(fz_ctx *, const uint8_t *, size_t n, int rows, int, int64_t, int *) { return recd("check_records", {U(n), U(rows)}); }
 int fz_launch_sign_encoded(fz_ctx *, const int32_t *, const int32_t *, size_t N, int l, int, int64_t, uint8_t *, int *) { return recd("sign_encoded", {U(N), U(l)}); }
 int fz_launch_sign_records(fz_ctx *, const uint8_t *, int, int64_t, const int32_t *, size_t N, int l, int, int64_t, uint8_t *, int *) { return recd("sign_records", {U(N), U(l)}); }
+int fz_launch_keygen_records(fz_ctx *, const int32_t *, const int32_t *, bool, size_t n, int l, int, int64_t, uint8_t *, int32_t *, int *) { return recd("keygen_records", {U(n), U(l)}); }
 int fz_launch_aggregate_encoded(fz_ctx *, const uint8_t *, const int32_t *, const int *, size_t N, int l, int, int64_t, int64_t *, int32_t *) { return recd("aggregate_encoded", {U(N), U(l)}); }
 int fz_launch_aggregate_encoded_ragged(fz_ctx *, const uint8_t *, const int32_t *, const int *, const size_t *off, size_t groups, int l, int, int64_t, int64_t *,
                                        size_t, int32_t *) { return recd("aggregate_encoded_ragged", {U(groups), U(off[groups]), U(l)}); }
@@ -243,9 +244,13 @@ int fz_launch_mt_sample(fz_ctx *, const unsigned long long *, size_t, int, uint3
 void fz_mt_init_table(uint32_t *) {}
 bool fz_challenge_wave_ok(const fz_scheme_params *) { return false; }
 void fz_challenge_weight_table(int, int, uint32_t *) {}
+// the setup of each unit that is not linked
 int fz_records_query_grid(fz_ctx *) { return FZ_OK; }
 int fz_aggregate_encoded_query_grid(fz_ctx *) { return FZ_OK; }
 int fz_sign_encoded_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_aggregate_many_encoded_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_sign_records_query_grid(fz_ctx *) { return FZ_OK; }
+int fz_keygen_records_query_grid(fz_ctx *) { return FZ_OK; }
 
 // ---- the checks ----
 static int g_fail = 0;
@@ -375,6 +380,15 @@ int main() {
       s = snap(); reached("total aggregate_encoded_ragged at 0xffffffbf", fz_aggregate_encoded_ragged_async(c, B, I, nullptr, off.data(), 1025, 4, 1, O64, ld, O32), s, "aggregate_encoded_ragged", {1025, 0xffffffbfull, 4});
       off[1025] = 0xffffffc0ull;
       s = snap(); refused("total aggregate_encoded_ragged at 0xffffffc0", fz_aggregate_encoded_ragged_async(c, B, I, nullptr, off.data(), 1025, 4, 1, O64, ld, O32), FZ_E_UNSUPPORTED, s); }
+    // fz_keygen_records_async: records of 2 l rows, and a workgroup per (key, half) in one grid: N <= 0x3fffffff (FZ_E_BADARG)
+    const int LK = 0x7fffffff / 512;                                         // 4194303: 2 l rows of degree 256
+    s = snap(); reached("rows*degree keygen_records at 0x7ffffe00", fz_keygen_records_async(c, I, I, 1, 2, LK, 1, BO, O32, ST), s, "keygen_records", {2, U(LK)});
+    s = snap(); refused("rows*degree keygen_records past 0x7fffffff", fz_keygen_records_async(c, I, I, 1, 2, LK + 1, 1, BO, O32, ST), FZ_E_BADARG, s);
+    s = snap(); refused("rows*degree keygen_records l at 2^30", fz_keygen_records_async(c, I, I, 1, 2, 1 << 30, 1, BO, O32, ST), FZ_E_BADARG, s);
+    g_label = "rows*degree keygen_records l at 2^30"; CHECK(strstr(fz_last_error(), "too many") != nullptr);      // (2 l is taken in 64 bits: the size's refusal, not the rows')
+    s = snap(); refused("rows*degree keygen_records l at 2^31 - 1", fz_keygen_records_async(c, I, I, 1, 2, 0x7fffffff, 1, BO, O32, ST), FZ_E_BADARG, s);
+    s = snap(); reached("N keygen_records at 0x3fffffff", fz_keygen_records_async(c, I, I, 1, 0x3fffffff, 4, 1, BO, O32, ST), s, "keygen_records", {0x3fffffffull, 4});
+    s = snap(); refused("N keygen_records at 0x40000000", fz_keygen_records_async(c, I, I, 1, 0x40000000, 4, 1, BO, O32, ST), FZ_E_BADARG, s);
     // fz_verify_encoded_async: l < 2^22 in the real launcher (512 records: one workgroup per record, no shared area)
     s = snap(); launched_as("l verify_encoded at 2^22 - 1", fz_verify_encoded_async(c, I, B, 512, (int)N22, 1, I, nullptr, nullptr, ST), s, "verify_encoded", {N22});
     s = snap(); refused("l verify_encoded at 2^22", fz_verify_encoded_async(c, I, B, 512, (int)N22 + 1, 1, I, nullptr, nullptr, ST), FZ_E_UNSUPPORTED, s);
@@ -499,7 +513,7 @@ LIMITS = [
     "N aggregate_core", "N aggregate_partial", "N aggregate_core_ragged group", "total aggregate_core_ragged",
     "rows*degree encode_records", "rows*degree decode_records", "rows*degree check_records", "rows*degree sign_encoded",
     "records product encode_records", "N aggregate_encoded", "N aggregate_encoded_ragged group", "total aggregate_encoded_ragged",
-    "l verify_encoded", "batch*2 keygen_core", "batch*2 keygen_core_bcast", "blocks matvec", "multi rows",
+    "rows*degree keygen_records", "N keygen_records", "l verify_encoded", "batch*2 keygen_core", "batch*2 keygen_core_bcast", "blocks matvec", "multi rows",
     "waves1 ntt_forward degree 256", "waves1 ntt_inverse degree 256", "waves1 ntt_forward degree 64",
     "wide_ntt rows", "wide_norm_weight rows", "threads fill_synthetic",
 ]

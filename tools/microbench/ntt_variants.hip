@@ -27,8 +27,6 @@ int fz_check_hip(hipError_t e, const char *what) {
     if (e != hipSuccess) { printf("HIP error in %s: %s\n", what, hipGetErrorString(e)); return FZ_E_HIP; }
     return FZ_OK;
 }
-// ... and from fz_records.hip (the resident-grid query calls it)
-int fz_records_query_grid(fz_ctx *) { return FZ_OK; }
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 
