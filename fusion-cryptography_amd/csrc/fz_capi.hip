@@ -5,30 +5,84 @@
 #include "../../include/fusion_hip.h"
 #include "../../include/fusion_hip_diag.h"
 
-#include <cstdio>
-#include <cstdlib>
+#include <cassert>
 #include <cstring>
 #include <algorithm>
 #include <vector>
 
+// ---- the rules the entries share, each written once (an entry keeps its own order of checks and its own wording) -----------------
+// degree 64 or 256: the degrees of the fused kernels
+static bool fused_degree(const fz_ctx *ctx) { return ctx->logd == 6 || ctx->logd == 8; }
+static int needs_fused(const fz_ctx *ctx, const char *what) {
+    return fused_degree(ctx) ? FZ_OK : fz_set_error(FZ_E_UNSUPPORTED, "%s needs the fused kernel (degree 64 or 256)", what);
+}
+static int needs_transforms(const fz_ctx *ctx) {
+    return ctx->logd >= 0 ? FZ_OK : fz_set_error(FZ_E_UNSUPPORTED, "ring-only context (created with root 0) has no transforms");
+}
+// the reference's __neg__ is -(x mod q) in [-(q-1), 0] (polynomials.py:155-163): the one value of the path that is NOT centred,
+// and for q >= 2^31 not an int32 either.  fz_pw_sub from a zero row gives the centred negation for every modulus.
+static int negation_fits(const fz_ctx *ctx) {
+    return ctx->q < 0x80000000u ? FZ_OK : fz_set_error(FZ_E_UNSUPPORTED, "-(x mod q) does not fit int32 for q >= 2^31: use fz_pw_sub(0, x), the centred negation");
+}
+// sums of N products are exact in int64 / fp64 below this many signers; `wording` (one %zu) is the entry's own
+constexpr size_t kExactSumLimit = (size_t)1 << 21;
+#define REQUIRE_EXACT_SUM(N, wording, shown) FZ_REQUIRE((N) < kExactSumLimit, wording, shown)
+// the aggregates of one launch (its grid's z), and the strides between their results: one aggregate needs none, more need at least a
+// result's length (need == 0: that result is not asked for)
+static bool groups_ok(size_t groups) { return groups <= 65535; }
+static bool strides_ok(size_t groups, size_t stride0, size_t need0, size_t stride1 = 0, size_t need1 = 0) {
+    return groups <= 1 || (stride0 >= need0 && stride1 >= need1);
+}
+// A host-pointer wrapper of a DEVICE entry that carves FZ_A_SCRATCH itself stages its operands in this area: the inner entry's
+// request may replace the first scratch, never the area under the operands.  (fz_poly_mul_host around fz_poly_mul.)
+constexpr int kHostStagingArea = FZ_A_SCRATCH2;
+// how an entry begins unless its own order says otherwise: its arguments (the context first), then the context's device made current
+#define FZ_ENTER(ctx, args_ok, ...) do { FZ_REQUIRE((ctx) && (args_ok), __VA_ARGS__); FZ_DEV(ctx); } while (0)
+
+// scratch of fz_verify_with_target_batch: observed [G][D] i32 | coef [G][l][D] i32 | max_abs [G][l] i64 | weight [G][l] i32.
+// fz_verify_core carves its own segments on top of the layout for one aggregate, which its inner call requests again.
+struct VerifyLayout { FzCarve c; size_t observed, coef, max_abs, weight; };
+static VerifyLayout verify_layout(const fz_ctx *ctx, size_t groups, int l) {
+    const size_t row = (size_t)ctx->degree * sizeof(int32_t), rows = groups * (size_t)l;
+    VerifyLayout v;
+    v.observed = v.c.take(groups * row), v.coef = v.c.take(rows * row);
+    v.max_abs = v.c.take(rows * sizeof(int64_t)), v.weight = v.c.take(rows * sizeof(int32_t));
+    return v;
+}
+
+// the five binary pointwise entries (fz_pw_neg: b = a)
+static int pw_binary(fz_ctx *ctx, int op, const int32_t *a, const int32_t *b, int32_t *out, size_t count) {
+    FZ_REQUIRE(ctx && (count == 0 || (a && b && out)), "NULL argument");
+    if (op == FZ_OP_NEG) FZ_TRY(negation_fits(ctx));
+    FZ_DEV(ctx);
+    return fz_launch_pw(ctx, op, a, b, out, count);
+}
+
+// sk_hat = NTT(every secret row); vk_{L,R} = A . sk_hat_{L,R}   (fusion/fusion.py:363-370); bcast: d_coef holds one polynomial per half
+static int keygen_core(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int32_t *d_sk_hat, int32_t *d_vk, size_t batch, int l, bool bcast) {
+    FZ_ENTER(ctx, l >= 1 && (batch == 0 || (d_A && d_coef && d_sk_hat && d_vk)), "bad argument");
+    if (batch == 0) return FZ_OK;
+    if (fused_degree(ctx) && batch * 2 <= 0x7fffffffu && !ctx->knob_unfused &&
+        ((((uintptr_t)d_A | (uintptr_t)d_coef | (uintptr_t)d_sk_hat) & 15) == 0))
+        return fz_launch_keygen_fused(ctx, d_A, d_coef, d_sk_hat, d_vk, batch * 2, l, bcast);   // one launch, sk_hat not re-read
+    // generic degrees: (bcast: expand the rows in sk_hat, transform in place,) then the products
+    if (bcast) FZ_TRY(fz_launch_bcast_rows(ctx, d_coef, d_sk_hat, batch * 2, l));
+    FZ_TRY(fz_launch_ntt(ctx, bcast ? d_sk_hat : d_coef, d_sk_hat, batch * 2 * (size_t)l, false));
+    return fz_launch_matvec(ctx, d_A, d_sk_hat, d_vk, batch * 2, l);
+}
+
 extern "C" {
 
 // ---- transforms ----------------------------------------------------------------------------
-int fz_ntt_forward(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch) {
-    FZ_REQUIRE(ctx && (batch == 0 || (d_in && d_out)), "NULL argument");
-    FZ_DEV(ctx);
-    return fz_launch_ntt(ctx, d_in, d_out, batch, false);
+static int ntt_dev(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch, bool inverse) {
+    FZ_ENTER(ctx, batch == 0 || (d_in && d_out), "NULL argument");
+    return fz_launch_ntt(ctx, d_in, d_out, batch, inverse);
 }
-
-int fz_ntt_inverse(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch) {
-    FZ_REQUIRE(ctx && (batch == 0 || (d_in && d_out)), "NULL argument");
-    FZ_DEV(ctx);
-    return fz_launch_ntt(ctx, d_in, d_out, batch, true);
-}
+int fz_ntt_forward(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch) { return ntt_dev(ctx, d_in, d_out, batch, false); }
+int fz_ntt_inverse(fz_ctx *ctx, const int32_t *d_in, int32_t *d_out, size_t batch) { return ntt_dev(ctx, d_in, d_out, batch, true); }
 
 static int ntt_host(fz_ctx *ctx, int32_t *h_data, size_t batch, bool inverse) {
-    FZ_REQUIRE(ctx && (batch == 0 || h_data), "NULL argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, batch == 0 || h_data, "NULL argument");
     if (batch == 0) return FZ_OK;
     const size_t bytes = batch * (size_t)ctx->degree * sizeof(int32_t);
     void *d = nullptr;
@@ -41,80 +95,53 @@ int fz_ntt_forward_host(fz_ctx *ctx, int32_t *h_data, size_t batch) { return ntt
 int fz_ntt_inverse_host(fz_ctx *ctx, int32_t *h_data, size_t batch) { return ntt_host(ctx, h_data, batch, true); }
 
 // ---- pointwise -------------------------------------------------------------------------------
-int fz_pw_mul(fz_ctx *ctx, const int32_t *a, const int32_t *b, int32_t *out, size_t count) {
-    FZ_REQUIRE(ctx && (count == 0 || (a && b && out)), "NULL argument");
-    FZ_DEV(ctx);
-    return fz_launch_pw(ctx, FZ_OP_MUL, a, b, out, count);
-}
-int fz_pw_add(fz_ctx *ctx, const int32_t *a, const int32_t *b, int32_t *out, size_t count) {
-    FZ_REQUIRE(ctx && (count == 0 || (a && b && out)), "NULL argument");
-    FZ_DEV(ctx);
-    return fz_launch_pw(ctx, FZ_OP_ADD, a, b, out, count);
-}
-int fz_pw_sub(fz_ctx *ctx, const int32_t *a, const int32_t *b, int32_t *out, size_t count) {
-    FZ_REQUIRE(ctx && (count == 0 || (a && b && out)), "NULL argument");
-    FZ_DEV(ctx);
-    return fz_launch_pw(ctx, FZ_OP_SUB, a, b, out, count);
-}
-int fz_pw_neg(fz_ctx *ctx, const int32_t *a, int32_t *out, size_t count) {
-    FZ_REQUIRE(ctx && (count == 0 || (a && out)), "NULL argument");
-    // the reference's __neg__ is -(x mod q) in [-(q-1), 0] (polynomials.py:155-163): the one value of the path that is NOT centred,
-    // and for q >= 2^31 not an int32 either.  fz_pw_sub from a zero row gives the centred negation for every modulus.
-    if (ctx->q >= 0x80000000u)
-        return fz_set_error(FZ_E_UNSUPPORTED, "-(x mod q) does not fit int32 for q >= 2^31: use fz_pw_sub(0, x), the centred negation");
-    FZ_DEV(ctx);
-    return fz_launch_pw(ctx, FZ_OP_NEG, a, a, out, count);
-}
-int fz_pw_mulacc(fz_ctx *ctx, int32_t *acc, const int32_t *a, const int32_t *b, size_t count) {
-    FZ_REQUIRE(ctx && (count == 0 || (acc && a && b)), "NULL argument");
-    FZ_DEV(ctx);
-    return fz_launch_pw(ctx, FZ_OP_MULACC, a, b, acc, count);
-}
+int fz_pw_mul(fz_ctx *ctx, const int32_t *a, const int32_t *b, int32_t *out, size_t count) { return pw_binary(ctx, FZ_OP_MUL, a, b, out, count); }
+int fz_pw_add(fz_ctx *ctx, const int32_t *a, const int32_t *b, int32_t *out, size_t count) { return pw_binary(ctx, FZ_OP_ADD, a, b, out, count); }
+int fz_pw_sub(fz_ctx *ctx, const int32_t *a, const int32_t *b, int32_t *out, size_t count) { return pw_binary(ctx, FZ_OP_SUB, a, b, out, count); }
+int fz_pw_neg(fz_ctx *ctx, const int32_t *a, int32_t *out, size_t count) { return pw_binary(ctx, FZ_OP_NEG, a, a, out, count); }
+int fz_pw_mulacc(fz_ctx *ctx, int32_t *acc, const int32_t *a, const int32_t *b, size_t count) { return pw_binary(ctx, FZ_OP_MULACC, a, b, acc, count); }
 int fz_pw_mul_bcast(fz_ctx *ctx, const int32_t *a, const int32_t *s, int32_t *out, size_t rows) {
-    FZ_REQUIRE(ctx && (rows == 0 || (a && s && out)), "NULL argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, rows == 0 || (a && s && out), "NULL argument");
     return fz_launch_pw_bcast(ctx, a, s, out, rows);
 }
 
 int fz_pw_binary_host(fz_ctx *ctx, int op, const int32_t *h_a, const int32_t *h_b, int32_t *h_out, size_t count) {
-    FZ_REQUIRE(ctx && op >= FZ_OP_MUL && op <= FZ_OP_NEG, "bad op %d", op);
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, op >= FZ_OP_MUL && op <= FZ_OP_NEG, "bad op %d", op);
     FZ_REQUIRE(count == 0 || (h_a && h_out && (op == FZ_OP_NEG || h_b)), "NULL argument");
-    if (op == FZ_OP_NEG && ctx->q >= 0x80000000u)       // see fz_pw_neg
-        return fz_set_error(FZ_E_UNSUPPORTED, "-(x mod q) does not fit int32 for q >= 2^31: use fz_pw_sub(0, x), the centred negation");
+    if (op == FZ_OP_NEG) FZ_TRY(negation_fits(ctx));
     if (count == 0) return FZ_OK;
-    const size_t seg = (count * sizeof(int32_t) + 255) & ~(size_t)255;
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, 3 * seg, &d));
-    int32_t *da = (int32_t *)d, *db = (int32_t *)((char *)d + seg), *dout = (int32_t *)((char *)d + 2 * seg);
-    FZ_TRY(fz_memcpy_h2d(ctx, da, h_a, count * sizeof(int32_t)));
-    if (op != FZ_OP_NEG) FZ_TRY(fz_memcpy_h2d(ctx, db, h_b, count * sizeof(int32_t)));
+    const size_t bytes = count * sizeof(int32_t);
+    FzCarve c;
+    const size_t oa = c.take(bytes), ob = c.take(bytes), oout = c.take(bytes);
+    FZ_TRY(c.fit(ctx, c.next));
+    int32_t *da = c.at<int32_t>(oa), *db = c.at<int32_t>(ob), *dout = c.at<int32_t>(oout);
+    FZ_TRY(fz_memcpy_h2d(ctx, da, h_a, bytes));
+    if (op != FZ_OP_NEG) FZ_TRY(fz_memcpy_h2d(ctx, db, h_b, bytes));
     FZ_TRY(fz_launch_pw(ctx, op, da, op == FZ_OP_NEG ? da : db, dout, count));
-    return fz_memcpy_d2h(ctx, h_out, dout, count * sizeof(int32_t));
+    return fz_memcpy_d2h(ctx, h_out, dout, bytes);
 }
 
 // ---- synthetic batches ----------------------------------------------------------------------------
 int fz_fill_synthetic(fz_ctx *ctx, int32_t *d_out, size_t count, uint64_t seed) {
-    FZ_REQUIRE(ctx && (count == 0 || d_out), "NULL argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, count == 0 || d_out, "NULL argument");
     return fz_launch_fill_synthetic(ctx, d_out, count, (unsigned long long)seed);
 }
 
 // ---- negacyclic product -------------------------------------------------------------------------
 int fz_poly_mul(fz_ctx *ctx, const int32_t *d_f, const int32_t *d_g, int32_t *d_out, size_t batch) {
-    FZ_REQUIRE(ctx && (batch == 0 || (d_f && d_g && d_out)), "NULL argument");
-    FZ_DEV(ctx);
-    if (ctx->logd < 0) return fz_set_error(FZ_E_UNSUPPORTED, "ring-only context (created with root 0) has no transforms");
+    FZ_ENTER(ctx, batch == 0 || (d_f && d_g && d_out), "NULL argument");
+    FZ_TRY(needs_transforms(ctx));
     if (batch == 0) return FZ_OK;
     if ((((uintptr_t)d_f | (uintptr_t)d_g | (uintptr_t)d_out) & 3) != 0)
         return fz_set_error(FZ_E_BADARG, "buffers must be 4-byte aligned");
-    if (!ctx->knob_unfused && (ctx->logd == 6 || ctx->logd == 8 || fz_polymul16_ok(ctx, d_f, d_g, d_out, batch)))
+    if (!ctx->knob_unfused && (fused_degree(ctx) || fz_polymul16_ok(ctx, d_f, d_g, d_out, batch)))
         return fz_launch_polymul_fused(ctx, d_f, d_g, d_out, batch);
     // generic degrees: NTT(f), NTT(g) into scratch, product in place, inverse into out
-    const size_t n = batch * (size_t)ctx->degree, seg = (n * sizeof(int32_t) + 255) & ~(size_t)255;
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, 2 * seg, &d));
-    int32_t *fh = (int32_t *)d, *gh = (int32_t *)((char *)d + seg);
+    const size_t n = batch * (size_t)ctx->degree;
+    FzCarve c;
+    const size_t of = c.take(n * sizeof(int32_t)), og = c.take(n * sizeof(int32_t));
+    FZ_TRY(c.fit(ctx, c.next));
+    int32_t *fh = c.at<int32_t>(of), *gh = c.at<int32_t>(og);
     FZ_TRY(fz_launch_ntt(ctx, d_f, fh, batch, false));
     FZ_TRY(fz_launch_ntt(ctx, d_g, gh, batch, false));
     FZ_TRY(fz_launch_pw(ctx, FZ_OP_MUL, fh, gh, fh, n));
@@ -122,14 +149,14 @@ int fz_poly_mul(fz_ctx *ctx, const int32_t *d_f, const int32_t *d_g, int32_t *d_
 }
 
 int fz_poly_mul_host(fz_ctx *ctx, const int32_t *h_f, const int32_t *h_g, int32_t *h_out, size_t batch) {
-    FZ_REQUIRE(ctx && (batch == 0 || (h_f && h_g && h_out)), "NULL argument");
-    FZ_DEV(ctx);
-    if (ctx->logd < 0) return fz_set_error(FZ_E_UNSUPPORTED, "ring-only context (created with root 0) has no transforms");
+    FZ_ENTER(ctx, batch == 0 || (h_f && h_g && h_out), "NULL argument");
+    FZ_TRY(needs_transforms(ctx));
     if (batch == 0) return FZ_OK;
-    const size_t bytes = batch * (size_t)ctx->degree * sizeof(int32_t), seg = (bytes + 255) & ~(size_t)255;
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, 2 * seg, &d, FZ_A_SCRATCH2));            // scratch2: the generic path of fz_poly_mul owns the first scratch
-    int32_t *df = (int32_t *)d, *dg = (int32_t *)((char *)d + seg);
+    const size_t bytes = batch * (size_t)ctx->degree * sizeof(int32_t);
+    FzCarve c;
+    const size_t of = c.take(bytes), og = c.take(bytes);
+    FZ_TRY(c.fit(ctx, c.next, kHostStagingArea));
+    int32_t *df = c.at<int32_t>(of), *dg = c.at<int32_t>(og);
     FZ_TRY(fz_memcpy_h2d(ctx, df, h_f, bytes));
     FZ_TRY(fz_memcpy_h2d(ctx, dg, h_g, bytes));
     FZ_TRY(fz_poly_mul(ctx, df, dg, df, batch));
@@ -138,78 +165,52 @@ int fz_poly_mul_host(fz_ctx *ctx, const int32_t *h_f, const int32_t *h_g, int32_
 
 // ---- matrix-vector ------------------------------------------------------------------------------
 int fz_matvec(fz_ctx *ctx, const int32_t *A, const int32_t *S, int32_t *out, size_t batch, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && (batch == 0 || (A && S && out)), "bad argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, l >= 1 && (batch == 0 || (A && S && out)), "bad argument");
     return fz_launch_matvec(ctx, A, S, out, batch, l);
 }
 
 int fz_matvec_host(fz_ctx *ctx, const int32_t *h_A, const int32_t *h_S, int32_t *h_out, size_t batch, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && (batch == 0 || (h_A && h_S && h_out)), "bad argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, l >= 1 && (batch == 0 || (h_A && h_S && h_out)), "bad argument");
     if (batch == 0) return FZ_OK;
     const size_t row = (size_t)ctx->degree * sizeof(int32_t);
     const size_t bA = (size_t)l * row, bS = batch * (size_t)l * row, bO = batch * row;
-    const size_t oS = (bA + 255) & ~(size_t)255, oO = oS + ((bS + 255) & ~(size_t)255);
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, oO + bO, &d));
-    char *base = (char *)d;
-    FZ_TRY(fz_memcpy_h2d(ctx, base, h_A, bA));
-    FZ_TRY(fz_memcpy_h2d(ctx, base + oS, h_S, bS));
-    FZ_TRY(fz_launch_matvec(ctx, (const int32_t *)base, (const int32_t *)(base + oS), (int32_t *)(base + oO), batch, l));
-    return fz_memcpy_d2h(ctx, h_out, base + oO, bO);
+    FzCarve c;
+    const size_t oA = c.take(bA), oS = c.take(bS), oO = c.take(bO);
+    FZ_TRY(c.fit(ctx, c.end));
+    FZ_TRY(fz_memcpy_h2d(ctx, c.at<void>(oA), h_A, bA));
+    FZ_TRY(fz_memcpy_h2d(ctx, c.at<void>(oS), h_S, bS));
+    FZ_TRY(fz_launch_matvec(ctx, c.at<const int32_t>(oA), c.at<const int32_t>(oS), c.at<int32_t>(oO), batch, l));
+    return fz_memcpy_d2h(ctx, h_out, c.at<void>(oO), bO);
 }
 
 // ---- fused scheme cores ---------------------------------------------------------------------------
-int fz_keygen_core(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int32_t *d_sk_hat, int32_t *d_vk,
-                   size_t batch, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && (batch == 0 || (d_A && d_coef && d_sk_hat && d_vk)), "bad argument");
-    FZ_DEV(ctx);
-    // sk_hat = NTT(every secret row); vk_{L,R} = A . sk_hat_{L,R}   (fusion/fusion.py:363-370)
-    if (batch == 0) return FZ_OK;
-    if ((ctx->logd == 6 || ctx->logd == 8) && batch * 2 <= 0x7fffffffu && !ctx->knob_unfused &&
-        ((((uintptr_t)d_A | (uintptr_t)d_coef | (uintptr_t)d_sk_hat) & 15) == 0))
-        return fz_launch_keygen_fused(ctx, d_A, d_coef, d_sk_hat, d_vk, batch * 2, l);   // one launch, sk_hat not re-read
-    FZ_TRY(fz_launch_ntt(ctx, d_coef, d_sk_hat, batch * 2 * (size_t)l, false));
-    return fz_launch_matvec(ctx, d_A, d_sk_hat, d_vk, batch * 2, l);
+int fz_keygen_core(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int32_t *d_sk_hat, int32_t *d_vk, size_t batch, int l) {
+    return keygen_core(ctx, d_A, d_coef, d_sk_hat, d_vk, batch, l, false);
 }
-
-int fz_keygen_core_bcast(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int32_t *d_sk_hat, int32_t *d_vk,
-                         size_t batch, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && (batch == 0 || (d_A && d_coef && d_sk_hat && d_vk)), "bad argument");
-    FZ_DEV(ctx);
-    if (batch == 0) return FZ_OK;
-    if ((ctx->logd == 6 || ctx->logd == 8) && batch * 2 <= 0x7fffffffu && !ctx->knob_unfused &&
-        ((((uintptr_t)d_A | (uintptr_t)d_coef | (uintptr_t)d_sk_hat) & 15) == 0))
-        return fz_launch_keygen_fused(ctx, d_A, d_coef, d_sk_hat, d_vk, batch * 2, l, true);
-    // generic degrees: expand the rows in sk_hat, transform in place, then the products
-    FZ_TRY(fz_launch_bcast_rows(ctx, d_coef, d_sk_hat, batch * 2, l));
-    FZ_TRY(fz_launch_ntt(ctx, d_sk_hat, d_sk_hat, batch * 2 * (size_t)l, false));
-    return fz_launch_matvec(ctx, d_A, d_sk_hat, d_vk, batch * 2, l);
+int fz_keygen_core_bcast(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int32_t *d_sk_hat, int32_t *d_vk, size_t batch, int l) {
+    return keygen_core(ctx, d_A, d_coef, d_sk_hat, d_vk, batch, l, true);
 }
 
 int fz_sign_core(fz_ctx *ctx, const int32_t *d_sk_hat, const int32_t *d_c_hat, int32_t *d_sig, size_t batch, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && (batch == 0 || (d_sk_hat && d_c_hat && d_sig)), "bad argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, l >= 1 && (batch == 0 || (d_sk_hat && d_c_hat && d_sig)), "bad argument");
     return fz_launch_sign(ctx, d_sk_hat, d_c_hat, d_sig, batch, l);
 }
 
 int fz_aggregate_partial_batch(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_alpha_hat, int64_t *d_partial,
                                size_t partial_stride, size_t groups, size_t N, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && d_partial && (N == 0 || groups == 0 || (d_sig && d_alpha_hat)), "bad argument");
-    FZ_DEV(ctx);
-    FZ_REQUIRE(N < ((size_t)1 << 21), "N=%zu too large for exact int64/fp64 accumulation (< 2^21)", N);
-    FZ_REQUIRE(groups <= 65535 && (groups <= 1 || partial_stride >= (size_t)l * ctx->degree), "bad groups / stride");
+    FZ_ENTER(ctx, l >= 1 && d_partial && (N == 0 || groups == 0 || (d_sig && d_alpha_hat)), "bad argument");
+    REQUIRE_EXACT_SUM(N, "N=%zu too large for exact int64/fp64 accumulation (< 2^21)", N);
+    FZ_REQUIRE(groups_ok(groups) && strides_ok(groups, partial_stride, (size_t)l * ctx->degree), "bad groups / stride");
     return fz_launch_aggregate(ctx, d_sig, d_alpha_hat, d_partial, partial_stride, nullptr, groups, N, l);
 }
 
 int fz_aggregate_target_partial_batch(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_alpha_hat, const int32_t *d_vkL,
                                       const int32_t *d_vkR, const int32_t *d_c_hat, int64_t *d_partial, size_t partial_stride,
                                       int64_t *d_target_partial, size_t target_stride, size_t groups, size_t N, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && d_partial && d_target_partial, "bad argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, l >= 1 && d_partial && d_target_partial, "bad argument");
     FZ_REQUIRE(N == 0 || groups == 0 || (d_sig && d_alpha_hat && d_vkL && d_vkR && d_c_hat), "NULL argument");
-    FZ_REQUIRE(N < ((size_t)1 << 21), "N=%zu too large for exact int64/fp64 accumulation (< 2^21)", N);
-    FZ_REQUIRE(groups <= 65535 && (groups <= 1 || (partial_stride >= (size_t)l * ctx->degree && target_stride >= (size_t)ctx->degree)),
+    REQUIRE_EXACT_SUM(N, "N=%zu too large for exact int64/fp64 accumulation (< 2^21)", N);
+    FZ_REQUIRE(groups_ok(groups) && strides_ok(groups, partial_stride, (size_t)l * ctx->degree, target_stride, (size_t)ctx->degree),
                "bad groups / strides");
     FZ_REQUIRE((((uintptr_t)d_vkL | (uintptr_t)d_vkR | (uintptr_t)d_c_hat | (uintptr_t)d_alpha_hat | (uintptr_t)d_sig) & 15) == 0,
                "inputs must be 16-byte aligned");
@@ -221,13 +222,12 @@ int fz_sign_aggregate_target_partial_batch(fz_ctx *ctx, const int32_t *d_sk_hat,
                                            const int32_t *d_vkL, const int32_t *d_vkR, int32_t *d_sig, int64_t *d_partial,
                                            size_t partial_stride, int64_t *d_target_partial, size_t target_stride, size_t groups,
                                            size_t N, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && d_partial, "bad argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, l >= 1 && d_partial, "bad argument");
     FZ_REQUIRE((d_vkL != nullptr) == (d_vkR != nullptr) && (d_vkL != nullptr) == (d_target_partial != nullptr),
                "verification keys and the target's partials come together or not at all");
     FZ_REQUIRE(N == 0 || groups == 0 || (d_sk_hat && d_c_hat && d_alpha_hat && d_sig), "NULL argument");
-    FZ_REQUIRE(N < ((size_t)1 << 21), "N=%zu too large for exact int64/fp64 accumulation (< 2^21)", N);
-    FZ_REQUIRE(groups <= 65535 && (groups <= 1 || (partial_stride >= (size_t)l * ctx->degree && (!d_vkL || target_stride >= (size_t)ctx->degree))),
+    REQUIRE_EXACT_SUM(N, "N=%zu too large for exact int64/fp64 accumulation (< 2^21)", N);
+    FZ_REQUIRE(groups_ok(groups) && strides_ok(groups, partial_stride, (size_t)l * ctx->degree, target_stride, d_vkL ? (size_t)ctx->degree : 0),
                "bad groups / strides");
     if (N == 0 || groups == 0) return FZ_OK;
     const int d = ctx->degree;
@@ -242,8 +242,7 @@ int fz_sign_aggregate_target_partial_batch(fz_ctx *ctx, const int32_t *d_sk_hat,
                                d_target_partial, target_stride);
 }
 
-int fz_aggregate_partial(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_alpha_hat, int64_t *d_partial,
-                         size_t N, int l) {
+int fz_aggregate_partial(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_alpha_hat, int64_t *d_partial, size_t N, int l) {
     return fz_aggregate_partial_batch(ctx, d_sig, d_alpha_hat, d_partial, 0, 1, N, l);
 }
 
@@ -254,7 +253,7 @@ static int aggregate_ragged(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_
     const size_t per = (size_t)l * ctx->degree;
     for (size_t g = 0; g < groups; ++g) {
         FZ_REQUIRE(h_offsets[g] <= h_offsets[g + 1], "offsets must not decrease");
-        FZ_REQUIRE(h_offsets[g + 1] - h_offsets[g] < ((size_t)1 << 21), "aggregate %zu: too many signers for exact accumulation (< 2^21)", g);
+        REQUIRE_EXACT_SUM(h_offsets[g + 1] - h_offsets[g], "aggregate %zu: too many signers for exact accumulation (< 2^21)", g);
     }
     FZ_REQUIRE(h_offsets[groups] < 0xffffffffull, "too many signers in one call");
     for (size_t g0 = 0; g0 < groups; g0 += (size_t)kFzRaggedMax) {
@@ -270,8 +269,7 @@ static int aggregate_ragged(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_
 
 int fz_aggregate_core_ragged(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_alpha_hat, const size_t *h_offsets, size_t groups,
                              int l, int32_t *d_out) {
-    FZ_REQUIRE(ctx && l >= 1 && h_offsets && (groups == 0 || (d_sig && d_alpha_hat && d_out)), "bad argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, l >= 1 && h_offsets && (groups == 0 || (d_sig && d_alpha_hat && d_out)), "bad argument");
     if (groups == 0) return FZ_OK;
     return aggregate_ragged(ctx, d_sig, d_alpha_hat, nullptr, nullptr, nullptr, h_offsets, groups, l, d_out, nullptr, 0, nullptr, 0);
 }
@@ -283,32 +281,28 @@ int fz_aggregate_target_partial_ragged(fz_ctx *ctx, const int32_t *d_sig, const 
     FZ_REQUIRE((d_sig == nullptr) == (d_partial == nullptr), "d_sig and d_partial go together (both NULL: verification targets only)");
     FZ_DEV(ctx);
     if (groups == 0) return FZ_OK;
-    FZ_REQUIRE(groups == 1 || ((!d_partial || partial_stride >= (size_t)l * ctx->degree) && target_stride >= (size_t)ctx->degree),
-               "bad strides");
+    FZ_REQUIRE(strides_ok(groups, partial_stride, d_partial ? (size_t)l * ctx->degree : 0, target_stride, (size_t)ctx->degree), "bad strides");
     return aggregate_ragged(ctx, d_sig, d_alpha_hat, d_vkL, d_vkR, d_c_hat, h_offsets, groups, l, nullptr, d_partial, partial_stride,
                             d_target_partial, target_stride);
 }
 
 int fz_reduce_i64(fz_ctx *ctx, const int64_t *d_in, int32_t *d_out, size_t count) {
-    FZ_REQUIRE(ctx && (count == 0 || (d_in && d_out)), "NULL argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, count == 0 || (d_in && d_out), "NULL argument");
     return fz_launch_reduce_i64(ctx, d_in, d_out, count);
 }
 
 int fz_aggregate_core(fz_ctx *ctx, const int32_t *d_sig, const int32_t *d_alpha_hat, int32_t *d_out, size_t N, int l) {
-    FZ_REQUIRE(ctx && l >= 1 && N >= 1 && d_sig && d_alpha_hat && d_out, "bad argument");
-    FZ_DEV(ctx);
-    FZ_REQUIRE(N < ((size_t)1 << 21), "N=%zu too large for exact fp64 accumulation (< 2^21)", N);
+    FZ_ENTER(ctx, l >= 1 && N >= 1 && d_sig && d_alpha_hat && d_out, "bad argument");
+    REQUIRE_EXACT_SUM(N, "N=%zu too large for exact fp64 accumulation (< 2^21)", N);
     return fz_launch_aggregate(ctx, d_sig, d_alpha_hat, nullptr, 0, d_out, 1, N, l);
 }
 
 int fz_target_partial_batch(fz_ctx *ctx, const int32_t *d_vkL, const int32_t *d_vkR, const int32_t *d_c_hat,
                             const int32_t *d_alpha_hat, int64_t *d_partial, size_t partial_stride, size_t groups,
                             size_t N) {
-    FZ_REQUIRE(ctx && d_partial && (N == 0 || groups == 0 || (d_vkL && d_vkR && d_c_hat && d_alpha_hat)), "bad argument");
-    FZ_DEV(ctx);
-    FZ_REQUIRE(N < ((size_t)1 << 21), "N=%zu too large (< 2^21)", N);
-    FZ_REQUIRE(groups <= 65535 && (groups <= 1 || partial_stride >= (size_t)ctx->degree), "bad groups / stride");
+    FZ_ENTER(ctx, d_partial && (N == 0 || groups == 0 || (d_vkL && d_vkR && d_c_hat && d_alpha_hat)), "bad argument");
+    REQUIRE_EXACT_SUM(N, "N=%zu too large (< 2^21)", N);
+    FZ_REQUIRE(groups_ok(groups) && strides_ok(groups, partial_stride, (size_t)ctx->degree), "bad groups / stride");
     return fz_launch_target_partial(ctx, d_vkL, d_vkR, d_c_hat, d_alpha_hat, d_partial, partial_stride, groups, N);
 }
 
@@ -318,61 +312,48 @@ int fz_target_partial(fz_ctx *ctx, const int32_t *d_vkL, const int32_t *d_vkR, c
 }
 
 int fz_norm_weight(fz_ctx *ctx, const int32_t *d_coef, size_t batch, int64_t *d_max_abs, int32_t *d_weight) {
-    FZ_REQUIRE(ctx && (batch == 0 || (d_coef && d_max_abs && d_weight)), "NULL argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, batch == 0 || (d_coef && d_max_abs && d_weight), "NULL argument");
     return fz_launch_norm_weight(ctx, d_coef, batch, d_max_abs, d_weight);
 }
 
 int fz_norm_weight_host(fz_ctx *ctx, const int32_t *h_coef, size_t batch, int64_t *h_max_abs, int32_t *h_weight) {
-    FZ_REQUIRE(ctx && (batch == 0 || (h_coef && h_max_abs && h_weight)), "NULL argument");
-    FZ_DEV(ctx);
+    FZ_ENTER(ctx, batch == 0 || (h_coef && h_max_abs && h_weight), "NULL argument");
     if (batch == 0) return FZ_OK;
-    const size_t bC = batch * (size_t)ctx->degree * sizeof(int32_t);
-    const size_t oM = (bC + 255) & ~(size_t)255, oW = oM + ((batch * sizeof(int64_t) + 255) & ~(size_t)255);
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, oW + batch * sizeof(int32_t), &d));
-    char *base = (char *)d;
-    FZ_TRY(fz_memcpy_h2d(ctx, base, h_coef, bC));
-    FZ_TRY(fz_launch_norm_weight(ctx, (const int32_t *)base, batch, (int64_t *)(base + oM), (int32_t *)(base + oW)));
-    FZ_TRY(fz_memcpy_d2h(ctx, h_max_abs, base + oM, batch * sizeof(int64_t)));
-    return fz_memcpy_d2h(ctx, h_weight, base + oW, batch * sizeof(int32_t));
+    const size_t bC = batch * (size_t)ctx->degree * sizeof(int32_t), bM = batch * sizeof(int64_t), bW = batch * sizeof(int32_t);
+    FzCarve c;
+    const size_t oC = c.take(bC), oM = c.take(bM), oW = c.take(bW);
+    FZ_TRY(c.fit(ctx, c.end));
+    FZ_TRY(fz_memcpy_h2d(ctx, c.at<void>(oC), h_coef, bC));
+    FZ_TRY(fz_launch_norm_weight(ctx, c.at<const int32_t>(oC), batch, c.at<int64_t>(oM), c.at<int32_t>(oW)));
+    FZ_TRY(fz_memcpy_d2h(ctx, h_max_abs, c.at<void>(oM), bM));
+    return fz_memcpy_d2h(ctx, h_weight, c.at<void>(oW), bW);
 }
 
 int fz_verify_with_target_batch(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const int32_t *d_target,
                                 size_t groups, int l, int64_t beta_vf, int64_t omega_vf, int *h_verdicts) {
-    FZ_REQUIRE(ctx && l >= 1 && groups >= 1 && groups <= 65535 && d_A && d_sig && d_target && h_verdicts, "bad argument");
-    FZ_DEV(ctx);
-    const size_t row = (size_t)ctx->degree * sizeof(int32_t), rows = groups * (size_t)l;
-    // scratch: observed [G][D] i32 | coef [G][l][D] i32 | max_abs [G][l] i64 | weight [G][l] i32
-    const size_t oC = (groups * row + 255) & ~(size_t)255;
-    const size_t oM = oC + ((rows * row + 255) & ~(size_t)255);
-    const size_t oW = oM + ((rows * sizeof(int64_t) + 255) & ~(size_t)255);
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, oW + rows * sizeof(int32_t), &d));
+    FZ_ENTER(ctx, l >= 1 && groups >= 1 && groups_ok(groups) && d_A && d_sig && d_target && h_verdicts, "bad argument");
+    VerifyLayout v = verify_layout(ctx, groups, l);
+    FZ_TRY(v.c.fit(ctx, v.c.end));                 // (the fused path below requests it too and never reads it)
     int *d_verdict = nullptr;
     FZ_TRY(fz_verdict_area(ctx, groups, &d_verdict));
-    if ((ctx->logd == 6 || ctx->logd == 8) && !ctx->knob_unfused) {
+    if (fused_degree(ctx) && !ctx->knob_unfused) {
         // one launch: sigma read once (matvec + inverse transforms + norm/weight + verdict fused)
         FZ_TRY(fz_launch_verify_fused(ctx, d_A, d_sig, d_target, groups, l, beta_vf, omega_vf, d_verdict));
-        return fz_memcpy_d2h(ctx, h_verdicts, d_verdict, groups * sizeof(int));
+    } else {
+        int32_t *observed = v.c.at<int32_t>(v.observed), *coef = v.c.at<int32_t>(v.coef), *wt = v.c.at<int32_t>(v.weight);
+        int64_t *mx = v.c.at<int64_t>(v.max_abs);
+        FZ_TRY(fz_launch_matvec(ctx, d_A, d_sig, observed, groups, l));               // fusion.py:715-717
+        FZ_TRY(fz_launch_ntt(ctx, d_sig, coef, groups * (size_t)l, true));            // fusion.py:690-692
+        FZ_TRY(fz_launch_norm_weight(ctx, coef, groups * (size_t)l, mx, wt));         // fusion.py:722-727
+        FZ_TRY(fz_launch_verdict(ctx, d_target, observed, mx, wt, groups, l, beta_vf, omega_vf, d_verdict));
     }
-    char *base = (char *)d;
-    int32_t *observed = (int32_t *)base, *coef = (int32_t *)(base + oC);
-    int64_t *mx = (int64_t *)(base + oM);
-    int32_t *wt = (int32_t *)(base + oW);
-    FZ_TRY(fz_launch_matvec(ctx, d_A, d_sig, observed, groups, l));               // fusion.py:715-717
-    FZ_TRY(fz_launch_ntt(ctx, d_sig, coef, rows, true));                          // fusion.py:690-692
-    FZ_TRY(fz_launch_norm_weight(ctx, coef, rows, mx, wt));                       // fusion.py:722-727
-    FZ_TRY(fz_launch_verdict(ctx, d_target, observed, mx, wt, groups, l, beta_vf, omega_vf, d_verdict));
     return fz_memcpy_d2h(ctx, h_verdicts, d_verdict, groups * sizeof(int));
 }
 
 int fz_verify_with_target_batch_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const int32_t *d_target,
                                       size_t groups, int l, int64_t beta_vf, int64_t omega_vf, int *d_verdicts) {
-    FZ_REQUIRE(ctx && l >= 1 && groups >= 1 && groups <= 65535 && d_A && d_sig && d_target && d_verdicts, "bad argument");
-    FZ_DEV(ctx);
-    if (ctx->logd != 6 && ctx->logd != 8)
-        return fz_set_error(FZ_E_UNSUPPORTED, "asynchronous verification needs the fused kernel (degree 64 or 256)");
+    FZ_ENTER(ctx, l >= 1 && groups >= 1 && groups_ok(groups) && d_A && d_sig && d_target && d_verdicts, "bad argument");
+    FZ_TRY(needs_fused(ctx, "asynchronous verification"));
     return fz_launch_verify_fused(ctx, d_A, d_sig, d_target, groups, l, beta_vf, omega_vf, d_verdicts);
 }
 
@@ -382,8 +363,7 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
     if (N == 0) return FZ_OK;
     FZ_REQUIRE(d_A && d_sig && d_vk && d_c_hat && d_verdicts, "NULL argument");
     FZ_REQUIRE((((uintptr_t)d_A | (uintptr_t)d_sig) & 15) == 0, "A and the signatures must be 16-byte aligned");
-    if (ctx->logd != 6 && ctx->logd != 8)
-        return fz_set_error(FZ_E_UNSUPPORTED, "per-signature verification needs the fused kernel (degree 64 or 256)");
+    FZ_TRY(needs_fused(ctx, "per-signature verification"));
     FZ_DEV(ctx);
     return fz_launch_verify_signatures(ctx, d_A, d_sig, d_vk, d_c_hat, N, l, beta, omega, d_verdicts);
 }
@@ -391,13 +371,11 @@ int fz_verify_signatures_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d
 int fz_verify_partials_batch_async(fz_ctx *ctx, const int32_t *d_A, const int64_t *d_partial, size_t partial_stride,
                                    const int64_t *d_target_partial, size_t target_stride, size_t groups, int l,
                                    int64_t beta_vf, int64_t omega_vf, int *d_verdicts) {
-    FZ_REQUIRE(ctx && l >= 1 && groups >= 1 && groups <= 65535 && d_A && d_partial && d_target_partial && d_verdicts, "bad argument");
-    FZ_DEV(ctx);
-    FZ_REQUIRE(groups == 1 || (partial_stride >= (size_t)l * ctx->degree && target_stride >= (size_t)ctx->degree), "bad strides");
+    FZ_ENTER(ctx, l >= 1 && groups >= 1 && groups_ok(groups) && d_A && d_partial && d_target_partial && d_verdicts, "bad argument");
+    FZ_REQUIRE(strides_ok(groups, partial_stride, (size_t)l * ctx->degree, target_stride, (size_t)ctx->degree), "bad strides");
     FZ_REQUIRE((((uintptr_t)d_partial | (uintptr_t)d_target_partial | (uintptr_t)d_A) & 15) == 0 && (partial_stride & 1) == 0,
                "partials must be 16-byte aligned");
-    if (ctx->logd != 6 && ctx->logd != 8)
-        return fz_set_error(FZ_E_UNSUPPORTED, "verification from int64 partials needs the fused kernel (degree 64 or 256)");
+    FZ_TRY(needs_fused(ctx, "verification from int64 partials"));
     return fz_launch_verify_fused_i64(ctx, d_A, d_partial, partial_stride, d_target_partial, target_stride, groups, l, beta_vf,
                                       omega_vf, d_verdicts);
 }
@@ -410,19 +388,15 @@ int fz_verify_with_target(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig,
 int fz_verify_core(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const int32_t *d_vkL, const int32_t *d_vkR,
                    const int32_t *d_c_hat, const int32_t *d_alpha_hat, size_t N, int l,
                    int64_t beta_vf, int64_t omega_vf, int *h_verdict) {
-    FZ_REQUIRE(ctx && l >= 1 && N >= 1 && d_A && d_sig && d_vkL && d_vkR && d_c_hat && d_alpha_hat && h_verdict,
-               "bad argument");
-    FZ_DEV(ctx);
-    // target lives behind the fz_verify_with_target scratch layout: allocate both up front
-    const size_t row = (size_t)ctx->degree * sizeof(int32_t);
-    const size_t inner = ((row + 255) & ~(size_t)255) + (((size_t)l * row + 255) & ~(size_t)255) +
-                         (((size_t)l * sizeof(int64_t) + 255) & ~(size_t)255) + (((size_t)l * sizeof(int32_t) + 255) & ~(size_t)255);
-    const size_t oP = inner, oT = oP + (((size_t)ctx->degree * sizeof(int64_t) + 255) & ~(size_t)255);
-    void *d = nullptr;
-    FZ_TRY(fz_scratch(ctx, oT + row, &d));
-    char *base = (char *)d;
-    int64_t *partial = (int64_t *)(base + oP);
-    int32_t *target = (int32_t *)(base + oT);
+    FZ_ENTER(ctx, l >= 1 && N >= 1 && d_A && d_sig && d_vkL && d_vkR && d_c_hat && d_alpha_hat && h_verdict, "bad argument");
+    // the int64 sums and the target live behind the layout of fz_verify_with_target, carved on top of it: both allocated up front
+    VerifyLayout v = verify_layout(ctx, 1, l);
+    const size_t inner = v.c.end;                  // what the call at the end requests
+    const size_t oP = v.c.take((size_t)ctx->degree * sizeof(int64_t)), oT = v.c.take((size_t)ctx->degree * sizeof(int32_t));
+    assert(v.c.end >= inner);                      // so that request fits the area sized here: it never replaces the area under the target
+    FZ_TRY(v.c.fit(ctx, v.c.end));
+    int64_t *partial = v.c.at<int64_t>(oP);
+    int32_t *target = v.c.at<int32_t>(oT);
     FZ_TRY(fz_target_partial(ctx, d_vkL, d_vkR, d_c_hat, d_alpha_hat, partial, N));   // fusion.py:706-714
     FZ_TRY(fz_launch_reduce_i64(ctx, partial, target, (size_t)ctx->degree));
     return fz_verify_with_target(ctx, d_A, d_sig, target, l, beta_vf, omega_vf, h_verdict);
@@ -431,9 +405,8 @@ int fz_verify_core(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_sig, const 
 
 // ---- many independent transforms in one dispatch -------------------------------------------------------
 int fz_ntt_multi(fz_ctx *ctx, const fz_ntt_job *h_jobs, size_t n_jobs) {
-    FZ_REQUIRE(ctx && (n_jobs == 0 || h_jobs), "NULL argument");
-    FZ_DEV(ctx);
-    if (ctx->logd < 0) return fz_set_error(FZ_E_UNSUPPORTED, "ring-only context (created with root 0) has no transforms");
+    FZ_ENTER(ctx, n_jobs == 0 || h_jobs, "NULL argument");
+    FZ_TRY(needs_transforms(ctx));
     for (size_t j = 0; j < n_jobs; ++j) {
         const fz_ntt_job &jb = h_jobs[j];
         FZ_REQUIRE(jb.rows == 0 || (jb.d_in && jb.d_out), "job %zu: NULL buffer", j);
@@ -441,7 +414,7 @@ int fz_ntt_multi(fz_ctx *ctx, const fz_ntt_job *h_jobs, size_t n_jobs) {
         if ((((uintptr_t)jb.d_in | (uintptr_t)jb.d_out) & 15) != 0 && ctx->logd >= 2)
             return fz_set_error(FZ_E_BADARG, "job %zu: transform buffers must be 16-byte aligned", j);
     }
-    if (ctx->logd != 6 && ctx->logd != 8) {              // other degrees: one launch per job (same results)
+    if (!fused_degree(ctx)) {                            // other degrees: one launch per job (same results)
         for (size_t j = 0; j < n_jobs; ++j)
             FZ_TRY(fz_launch_ntt(ctx, h_jobs[j].d_in, h_jobs[j].d_out, h_jobs[j].rows, h_jobs[j].inverse != 0));
         return FZ_OK;
@@ -468,8 +441,10 @@ int fz_ntt_multi(fz_ctx *ctx, const fz_ntt_job *h_jobs, size_t n_jobs) {
     return fz_launch_ntt_multi(ctx, J);
 }
 
-// the next staging slot, at least `bytes` long and no longer read by any launch (fz_internal.h)
-static int challenge_stage(fz_ctx *ctx, size_t bytes, fz_ctx::FzStage **out) {
+// ---- the pinned staging slots (fz_internal.h), shared by the challenge pipeline's wave form and the sampler ---------------------
+// The protocol: stage_take, fill the slot, the launches that read it, stage_release with what they returned.
+// stage_take: the next slot, at least `bytes` long and no longer read by any launch
+static int stage_take(fz_ctx *ctx, size_t bytes, fz_ctx::FzStage **out) {
     fz_ctx::FzStage &st = ctx->chal_stage[ctx->chal_stage_next];
     ctx->chal_stage_next ^= 1;
     if (!st.ev) FZ_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), "staging event");
@@ -483,17 +458,33 @@ static int challenge_stage(fz_ctx *ctx, size_t bytes, fz_ctx::FzStage **out) {
     *out = &st;
     return FZ_OK;
 }
+// stage_release: the slot's event is recorded and the slot marked in use BEFORE the launches' code `rc` is looked at (a sequence that
+// failed half-way may have queued a reader); -> rc, or the record's own error
+static int stage_release(fz_ctx *ctx, fz_ctx::FzStage *st, int rc) {
+    FZ_HIP(hipEventRecord(st->ev, ctx->stream), "staging event record");
+    st->busy = 1;
+    return rc;
+}
 
 // ---- the challenge pipeline on the device (device half) ---------------------------------------------
 // the pre-hashed messages come either as h_prehash [N][32] (computed by the caller, fz_hash_messages) or are computed here,
 // on the device, from the messages themselves (h_msgs back to back, h_msg_off [N + 1]); h_prehash_out (optional, with
 // messages only) receives them
-static int challenge_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash, const char *h_msgs,
-                         const size_t *h_msg_off, uint8_t *h_prehash_out, size_t N, int32_t *d_out, bool transform) {
-    FZ_REQUIRE(ctx && P && (N == 0 || (d_vk && (h_prehash || h_msg_off) && d_out)), "NULL argument");
-    if (!h_prehash && N) {
-        FZ_REQUIRE(h_msg_off[N] == h_msg_off[0] || h_msgs, "NULL argument");
-        for (size_t i = 0; i < N; ++i) FZ_REQUIRE(h_msg_off[i] <= h_msg_off[i + 1], "message offsets must not decrease");
+struct ChalCall {
+    fz_ctx *ctx; const fz_scheme_params *P; const int32_t *d_vk; const uint8_t *h_prehash; const char *h_msgs; const size_t *h_msg_off;
+    uint8_t *h_prehash_out; size_t N; int32_t *d_out; bool transform;         // what the entry was handed
+    size_t text_stride; int out_blocks, index_bytes;     // challenge_geometry: bytes of a signer's text row, blocks of SHAKE output, the decoder's index bytes
+    const uint32_t *d_tab;                               // challenge_table
+};
+static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets travel as 64-bit words");
+
+static int challenge_checks(const ChalCall &c) {
+    fz_ctx *ctx = c.ctx;
+    const fz_scheme_params *P = c.P;
+    FZ_REQUIRE(ctx && P && (c.N == 0 || (c.d_vk && (c.h_prehash || c.h_msg_off) && c.d_out)), "NULL argument");
+    if (!c.h_prehash && c.N) {
+        FZ_REQUIRE(c.h_msg_off[c.N] == c.h_msg_off[0] || c.h_msgs, "NULL argument");
+        for (size_t i = 0; i < c.N; ++i) FZ_REQUIRE(c.h_msg_off[i] <= c.h_msg_off[i + 1], "message offsets must not decrease");
     }
     FZ_DEV(ctx);
     if (!fz_host_params_ok(P)) return fz_set_error(FZ_E_BADARG, "bad scheme parameters");
@@ -502,99 +493,123 @@ static int challenge_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *
     if (fz_capturing(ctx)) return fz_set_error(FZ_E_BADARG, "the challenge pipeline uploads the pre-hashed messages: not during graph capture");
     const long long bound = std::max<long long>(1, std::min<long long>((long long)P->modulus / 2, P->beta_ch));
     if (bound != 1 || P->degree > 256 || P->degree < 4 || (P->degree & (P->degree - 1)) || P->omega_ch > P->degree ||
-        (((uintptr_t)d_vk | (uintptr_t)d_out) & 15))
+        (((uintptr_t)c.d_vk | (uintptr_t)c.d_out) & 15))
         return fz_set_error(FZ_E_UNSUPPORTED, "device challenge pipeline: ternary challenges (norm bound 1), degree 4..256 and "
                                               "16-byte aligned rows only; use fz_challenge_coefficients (host)");
-    if (transform && ctx->logd < 0) return fz_set_error(FZ_E_UNSUPPORTED, "ring-only context (created with root 0) has no transforms");
-    if (N == 0) return FZ_OK;
-    int sb = 0, cb = 0, ib = 0;
-    const size_t needed = fz_host_challenge_needed_bytes(P, &sb, &cb, &ib);
-    const int out_blocks = (int)((needed + 135) / 136);
+    if (c.transform) FZ_TRY(needs_transforms(ctx));
+    return FZ_OK;
+}
+
+static int challenge_geometry(ChalCall &c) {
+    int sb = 0, cb = 0;
+    const size_t needed = fz_host_challenge_needed_bytes(c.P, &sb, &cb, &c.index_bytes);
+    c.out_blocks = (int)((needed + 135) / 136);
     // longest possible text: fixed pieces + 2*degree values of up to 11 characters + separators + 78 digits
     char t0[384], t1[384], t2[16];
     int n0, n1, n2;
-    fz_host_vk_text_parts(P, t0, &n0, t1, &n1, t2, &n2, 384);
+    fz_host_vk_text_parts(c.P, t0, &n0, t1, &n1, t2, &n2, 384);
     if (n0 < 0) return fz_set_error(FZ_E_UNSUPPORTED, "verification-key text pieces do not fit");
-    const size_t max_len = (size_t)n0 + n1 + n2 + (size_t)2 * P->degree * 13 + 78;
+    const size_t max_len = (size_t)n0 + n1 + n2 + (size_t)2 * c.P->degree * 13 + 78;
     size_t blocks = max_len / 136 + 1;
     blocks += blocks & 1;                                   // even: rows stay 16-byte aligned
-    const size_t text_stride = blocks * 136;
-    if (!ctx->area[FZ_A_CHAL_TAB].p || ctx->chal_tab_ib != ib || ctx->chal_tab_degree != P->degree) {
-        std::vector<uint32_t> tab((size_t)(P->degree + 1) * 16);
-        fz_challenge_weight_table(ib, P->degree, tab.data());
+    c.text_stride = blocks * 136;
+    return FZ_OK;
+}
+
+// the decoder's weight table, cached in FZ_A_CHAL_TAB for the (index bytes, degree) it was built for
+static int challenge_table(ChalCall &c) {
+    fz_ctx *ctx = c.ctx;
+    const int ib = c.index_bytes, degree = c.P->degree;
+    if (!ctx->area[FZ_A_CHAL_TAB].p || ctx->chal_tab_ib != ib || ctx->chal_tab_degree != degree) {
+        std::vector<uint32_t> tab((size_t)(degree + 1) * 16);
+        fz_challenge_weight_table(ib, degree, tab.data());
         ctx->chal_tab_degree = 0;                            // (no table is built for degree 0: a failure below leaves none that counts)
         FZ_TRY(fz_area_replace(ctx, FZ_A_CHAL_TAB, tab.size() * 4));
         FZ_HIP(hipMemcpy(ctx->area[FZ_A_CHAL_TAB].p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice), "table upload");
         ctx->chal_tab_ib = ib;
-        ctx->chal_tab_degree = P->degree;
+        ctx->chal_tab_degree = degree;
     }
-    const uint32_t *d_chal_tab = (const uint32_t *)ctx->area[FZ_A_CHAL_TAB].p;
+    c.d_tab = (const uint32_t *)ctx->area[FZ_A_CHAL_TAB].p;
+    return FZ_OK;
+}
+
+// One launch, nothing uploaded: the kernel reads the messages (or digests) from pinned host memory and leaves the
+// digests there.  The call returns without synchronising unless the caller wants the digests.
+static int challenge_wave_form(const ChalCall &c) {
+    fz_ctx *ctx = c.ctx;
+    const size_t N = c.N, msg_bytes = c.h_prehash ? 0 : c.h_msg_off[N] - c.h_msg_off[0];
+    const size_t o_pre = 0, o_off = N * 32, o_msg = o_off + (N + 1) * 8;
+    const bool digests_out = !c.h_prehash && c.h_prehash_out;
+    fz_ctx::FzStage *st = nullptr;
+    FZ_TRY(stage_take(ctx, o_msg + msg_bytes + 64, &st));
+    if (c.h_prehash) {
+        memcpy(st->h + o_pre, c.h_prehash, N * 32);
+    } else {
+        memcpy(st->h + o_off, c.h_msg_off, (N + 1) * 8);
+        if (msg_bytes) memcpy(st->h + o_msg, c.h_msgs + c.h_msg_off[0], msg_bytes);
+    }
+    int rc = fz_launch_challenge_wave(ctx, c.P, c.d_vk, c.h_prehash ? st->h + o_pre : nullptr, st->h + o_msg, (const unsigned long long *)(st->h + o_off),
+                                      digests_out ? st->h + o_pre : nullptr, N, c.text_stride, c.out_blocks, c.d_tab, c.d_out);
+    if (rc == FZ_OK && c.transform) rc = fz_launch_ntt(ctx, c.d_out, c.d_out, N, false);
+    FZ_TRY(stage_release(ctx, st, rc));
+    if (digests_out) {
+        FZ_HIP(hipStreamSynchronize(ctx->stream), "digest sync");
+        memcpy(c.h_prehash_out, st->h + o_pre, N * 32);
+    }
+    return FZ_OK;
+}
+
+// The three-kernel pipeline in passes of 65536 signers = two waves of 32 signers on each of the chip's 1024 SIMDs (a second wave per
+// SIMD fills the issue slots one wave alone leaves empty); bounds the scratch at ~16 KB per signer
+static int challenge_chunked_form(const ChalCall &c) {
+    fz_ctx *ctx = c.ctx;
+    const size_t chunk = 65536;
+    for (size_t base = 0; base < c.N; base += chunk) {
+        const size_t n = std::min(chunk, c.N - base);
+        const size_t xstride = (n + 63) & ~(size_t)63;
+        const size_t msg_bytes = c.h_prehash ? 0 : c.h_msg_off[base + n] - c.h_msg_off[base];
+        FzCarve s;
+        const size_t o_pre = s.take(n * 32), o_nb = s.take(n * 4), o_text = s.take(n * c.text_stride);
+        const size_t o_xof = s.take(((size_t)c.out_blocks * 34 + 1) * xstride * 4);     // + one spare word row (decoder)
+        const size_t with_digests = s.next;                   // digests: the three segments below are not allocated
+        const size_t o_off = s.take((n + 1) * 8);
+        const size_t o_dec = s.take(n * 64);                  // [n][16] words: the integers in base 10^9
+        const size_t o_msg = s.take_packed(msg_bytes);        // (64-aligned)
+        FZ_TRY(s.fit(ctx, c.h_prehash ? with_digests : s.next));
+        uint8_t *sp = s.at<uint8_t>(0);
+        if (c.h_prehash) {
+            FZ_HIP(hipMemcpyAsync(sp + o_pre, c.h_prehash + 32 * base, n * 32, hipMemcpyHostToDevice, ctx->stream), "upload of the pre-hashed messages");
+        } else {
+            FZ_HIP(hipMemcpyAsync(sp + o_off, c.h_msg_off + base, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream), "upload of the message offsets");
+            if (msg_bytes)
+                FZ_HIP(hipMemcpyAsync(sp + o_msg, c.h_msgs + c.h_msg_off[base], msg_bytes, hipMemcpyHostToDevice, ctx->stream), "upload of the messages");
+            FZ_TRY(fz_launch_prehash(ctx, c.P, sp + o_msg, (const unsigned long long *)(sp + o_off), n, sp + o_pre, (uint32_t *)(sp + o_dec)));
+            if (c.h_prehash_out)
+                FZ_HIP(hipMemcpyAsync(c.h_prehash_out + 32 * base, sp + o_pre, n * 32, hipMemcpyDeviceToHost, ctx->stream), "download of the pre-hashed messages");
+        }
+        FZ_HIP(hipStreamSynchronize(ctx->stream), "upload sync");      // the caller's buffers have been consumed when this returns
+        FZ_TRY(fz_launch_challenge(ctx, c.P, c.d_vk + base * 2 * (size_t)c.P->degree, sp + o_pre,
+                                   c.h_prehash ? nullptr : (const uint32_t *)(sp + o_dec), n, sp + o_text, c.text_stride,
+                                   (int *)(sp + o_nb), (uint32_t *)(sp + o_xof), xstride, c.out_blocks, c.d_tab,
+                                   c.d_out + base * (size_t)c.P->degree));
+    }
+    if (c.transform) return fz_launch_ntt(ctx, c.d_out, c.d_out, c.N, false);
+    return FZ_OK;
+}
+
+static int challenge_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash, const char *h_msgs,
+                         const size_t *h_msg_off, uint8_t *h_prehash_out, size_t N, int32_t *d_out, bool transform) {
+    ChalCall c{ctx, P, d_vk, h_prehash, h_msgs, h_msg_off, h_prehash_out, N, d_out, transform, 0, 0, 0, nullptr};
+    FZ_TRY(challenge_checks(c));
+    if (N == 0) return FZ_OK;
+    FZ_TRY(challenge_geometry(c));
+    FZ_TRY(challenge_table(c));
     // Which form.  Up to kWaveFormMax signers per call every signer gets a WAVE (fz_launch_challenge_wave: the chain of ~108
     // permutations at 24 instructions + 4 gathers per round, text and stream in LDS); beyond, the three-kernel pipeline with 32
     // or 64 signers per wave has the higher throughput (profiles/r06_challenge_pipeline.txt).
     constexpr size_t kWaveFormMax = 4608;                    // 4096 signers: 0.67 ms against 0.77; 5120: 0.85 against 0.79
     const bool wave_form = fz_challenge_wave_ok(P) && (ctx->knob_shake_full == 3 || (ctx->knob_shake_full == 0 && N <= kWaveFormMax));
-    if (wave_form) {
-        // One launch, nothing uploaded: the kernel reads the messages (or digests) from pinned host memory and leaves the
-        // digests there.  The call returns without synchronising unless the caller wants the digests.
-        const size_t msg_bytes = h_prehash ? 0 : h_msg_off[N] - h_msg_off[0];
-        const size_t o_pre = 0, o_off = N * 32, o_msg = o_off + (N + 1) * 8;
-        fz_ctx::FzStage *st = nullptr;
-        FZ_TRY(challenge_stage(ctx, o_msg + msg_bytes + 64, &st));
-        if (h_prehash) {
-            memcpy(st->h + o_pre, h_prehash, N * 32);
-        } else {
-            static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets travel as 64-bit words");
-            memcpy(st->h + o_off, h_msg_off, (N + 1) * 8);
-            if (msg_bytes) memcpy(st->h + o_msg, h_msgs + h_msg_off[0], msg_bytes);
-        }
-        int rc = fz_launch_challenge_wave(ctx, P, d_vk, h_prehash ? st->h + o_pre : nullptr, st->h + o_msg, (const unsigned long long *)(st->h + o_off),
-                                          (!h_prehash && h_prehash_out) ? st->h + o_pre : nullptr, N, text_stride, out_blocks, d_chal_tab, d_out);
-        if (rc == FZ_OK && transform) rc = fz_launch_ntt(ctx, d_out, d_out, N, false);
-        FZ_HIP(hipEventRecord(st->ev, ctx->stream), "staging event record");
-        st->busy = 1;
-        if (rc != FZ_OK) return rc;
-        if (!h_prehash && h_prehash_out) {
-            FZ_HIP(hipStreamSynchronize(ctx->stream), "digest sync");
-            memcpy(h_prehash_out, st->h + o_pre, N * 32);
-        }
-        return FZ_OK;
-    }
-    // signers per pass: 65536 = two waves of 32 signers on each of the chip's 1024 SIMDs (a second wave per SIMD fills the
-    // issue slots one wave alone leaves empty); bounds the scratch at ~16 KB per signer
-    const size_t chunk = 65536;
-    for (size_t base = 0; base < N; base += chunk) {
-        const size_t n = std::min(chunk, N - base);
-        const size_t xstride = (n + 63) & ~(size_t)63;
-        const size_t o_pre = 0, o_nb = (n * 32 + 255) & ~(size_t)255, o_text = o_nb + ((n * 4 + 255) & ~(size_t)255);
-        const size_t o_xof = o_text + ((n * text_stride + 255) & ~(size_t)255);
-        const size_t o_off = o_xof + ((((size_t)out_blocks * 34 + 1) * xstride * 4 + 255) & ~(size_t)255);    // + one spare word row (decoder)
-        const size_t msg_bytes = h_prehash ? 0 : h_msg_off[base + n] - h_msg_off[base];
-        const size_t o_dec = o_off + (((n + 1) * 8 + 255) & ~(size_t)255);              // [n][16] words: the integers in base 10^9
-        const size_t o_msg = o_dec + n * 64;
-        const size_t total = h_prehash ? o_off : o_msg + ((msg_bytes + 255) & ~(size_t)255);
-        void *scr = nullptr;
-        FZ_TRY(fz_scratch(ctx, total, &scr));
-        uint8_t *sp = (uint8_t *)scr;
-        if (h_prehash) {
-            FZ_HIP(hipMemcpyAsync(sp + o_pre, h_prehash + 32 * base, n * 32, hipMemcpyHostToDevice, ctx->stream), "upload of the pre-hashed messages");
-        } else {
-            static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets travel as 64-bit words");
-            FZ_HIP(hipMemcpyAsync(sp + o_off, h_msg_off + base, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream), "upload of the message offsets");
-            if (msg_bytes)
-                FZ_HIP(hipMemcpyAsync(sp + o_msg, h_msgs + h_msg_off[base], msg_bytes, hipMemcpyHostToDevice, ctx->stream), "upload of the messages");
-            FZ_TRY(fz_launch_prehash(ctx, P, sp + o_msg, (const unsigned long long *)(sp + o_off), n, sp + o_pre, (uint32_t *)(sp + o_dec)));
-            if (h_prehash_out)
-                FZ_HIP(hipMemcpyAsync(h_prehash_out + 32 * base, sp + o_pre, n * 32, hipMemcpyDeviceToHost, ctx->stream), "download of the pre-hashed messages");
-        }
-        FZ_HIP(hipStreamSynchronize(ctx->stream), "upload sync");      // the caller's buffers have been consumed when this returns
-        FZ_TRY(fz_launch_challenge(ctx, P, d_vk + base * 2 * (size_t)P->degree, sp + o_pre,
-                                   h_prehash ? nullptr : (const uint32_t *)(sp + o_dec), n, sp + o_text, text_stride,
-                                   (int *)(sp + o_nb), (uint32_t *)(sp + o_xof), xstride, out_blocks, d_chal_tab,
-                                   d_out + base * (size_t)P->degree));
-    }
-    if (transform) return fz_launch_ntt(ctx, d_out, d_out, N, false);
-    return FZ_OK;
+    return wave_form ? challenge_wave_form(c) : challenge_chunked_form(c);
 }
 
 int fz_challenge_coefficients_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash,
@@ -656,15 +671,12 @@ int fz_sample_secret_polys_dev(fz_ctx *ctx, const uint64_t *h_seeds, size_t N, i
     // seeds in place and store the flag there, so the call is two launches and one synchronisation -- no memset, no pageable upload,
     // no download (0.098 -> 0.078 ms per 1024 keys: most of what was left beside the two kernels' 57 us)
     fz_ctx::FzStage *st = nullptr;
-    FZ_TRY(challenge_stage(ctx, 64 + N * 8, &st));
+    FZ_TRY(stage_take(ctx, 64 + N * 8, &st));
     volatile int *h_fail = reinterpret_cast<volatile int *>(st->h);
     *h_fail = 0;
     memcpy(st->h + 64, h_seeds, N * 8);
-    int rc = fz_launch_mt_sample(ctx, reinterpret_cast<const unsigned long long *>(st->h + 64), N, degree, (uint32_t)bound, kbits,
-                                 ctx->d_mt_init, d_out, reinterpret_cast<int *>(st->h), d_state);
-    FZ_HIP(hipEventRecord(st->ev, ctx->stream), "staging event record");
-    st->busy = 1;
-    if (rc != FZ_OK) return rc;
+    FZ_TRY(stage_release(ctx, st, fz_launch_mt_sample(ctx, reinterpret_cast<const unsigned long long *>(st->h + 64), N, degree, (uint32_t)bound, kbits,
+                                                      ctx->d_mt_init, d_out, reinterpret_cast<int *>(st->h), d_state)));
     FZ_HIP(hipStreamSynchronize(ctx->stream), "sampler sync");
     const int fail = *h_fail;
     if (fail) return fz_set_error(FZ_E_UNSUPPORTED, "device sampler ran out of generator output for a seed; use fz_sample_secret_polys");

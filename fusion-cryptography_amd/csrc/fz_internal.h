@@ -229,6 +229,19 @@ static inline int fz_scratch(fz_ctx *ctx, size_t bytes, void **out, int which = 
     *out = ctx->area[which].p;
     return FZ_OK;
 }
+// The layout of one entry's scratch, written once: take(bytes) -> the segment's offset, each segment starting on the next multiple
+// of 256 behind the one before; take_packed: straight behind it instead.  end = where the last segment ends (what most entries
+// request), next = where take() would put another (the request of an entry that rounds its last segment too, and what a layout
+// occupies in front of segments carved on top of it).  fit() sizes the area for `bytes` of it; at<T>(offset) = the segment there.
+struct FzCarve {
+    size_t end = 0, next = 0;
+    void *base = nullptr;                          // (the area, once fit() has sized it)
+    size_t take(size_t bytes) { return place(next, bytes); }
+    size_t take_packed(size_t bytes) { return place(end, bytes); }
+    int fit(fz_ctx *ctx, size_t bytes, int which = FZ_A_SCRATCH) { return fz_scratch(ctx, bytes, &base, which); }
+    template <class T> T *at(size_t offset) const { return (T *)((char *)base + offset); }
+    size_t place(size_t offset, size_t bytes) { end = offset + bytes; next = offset + ((bytes + 255) & ~(size_t)255); return offset; }
+};
 int fz_verdict_area(fz_ctx *ctx, size_t groups, int **d_verdict);
 int fz_verify_scratch(fz_ctx *ctx, size_t groups, size_t doubles_per_group, double **part, int **state);
 int fz_agg_scratch(fz_ctx *ctx, size_t tiles, size_t tile_words, unsigned long long **acc);

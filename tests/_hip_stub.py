@@ -46,7 +46,7 @@ static bool g_report_capture = false;                 // control: hipStreamIsCap
 static long g_fail_at = -1, g_allocs = 0;             // control: allocations [g_fail_at, g_fail_at + g_fail_n) fail
 static int g_fail_n = 1;
 static long g_fail_event_at = -1, g_events = 0;       // ... and this event creation
-static bool g_copy_nothing = false;                   // control: hipMemcpy logs and touches no memory (a driver whose pointers are dummies)
+static bool g_copy_nothing = false;                   // control: hipMemcpy and hipMemcpyAsync log and touch no memory (a driver whose pointers are dummies)
 static size_t g_fake_above = 0;                       // control: a hipMalloc of more bytes than this (0: never) is logged with its size, backed by 1 byte
 static int stub_tid() {
     static std::atomic<int> next(0);
@@ -114,7 +114,7 @@ hipError_t hipHostMalloc(void **p, size_t n, unsigned) {
 }
 hipError_t hipHostFree(void *p) { rec("hipHostFree", p, 0, nullptr, nullptr, -1, p ? -1 : 0); free(p); return hipSuccess; }
 hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { rec("hipMemcpy", d, n, nullptr, s, (int)k); if (!g_copy_nothing) memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) { rec("hipMemcpyAsync", d, n, st, s, (int)k); memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) { rec("hipMemcpyAsync", d, n, st, s, (int)k); if (!g_copy_nothing) memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st) { rec("hipMemsetAsync", d, n, st); if (n) memset(d, v, n); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t st) { rec("hipStreamSynchronize", nullptr, 0, st); return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return new_stream(s); }
