@@ -336,6 +336,13 @@ int fz_launch_sign_records(fz_ctx *ctx, const uint8_t *key_bytes, int wk, int64_
 int fz_launch_keygen_records(fz_ctx *ctx, const int32_t *A, const int32_t *coef, bool rows, size_t n, int l, int wk, int64_t key_bound,
                              uint8_t *d_bytes, int32_t *d_vk, int *d_status);
 
+// verification keys straight from "secret" records (fz_vk_records.hip; degree 64 / 256): d_vk [n][2][degree] = per half
+// cent(sum_k cent(FWD(s_k) (.) A_k)) from key records [n][2][l][degree] of wk-bit fields s + key_bound and A [l][degree], any int32;
+// d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING (a key field above 2 key_bound); refused keys' vk zeroed.  2 n fits a
+// grid's first dimension (the entry sees to it); FZ_E_UNSUPPORTED for l >= 2^22
+int fz_launch_vk_records(fz_ctx *ctx, const int32_t *A, const uint8_t *key_bytes, int wk, int64_t key_bound, size_t n, int l,
+                         int32_t *d_vk, int *d_status);
+
 // the byte encoding's consumers without rows (fz_aggregate_encoded.hip; degree 64 / 256): the range check of a byte stream alone
 // (d_status [n] cleared, then 0 or FZ_VERDICT_ENCODING), and the aggregate of N signature records of l rows straight from
 // their bytes: d_partial [l][degree] int64 zeroed, then sum_i cent(NTT(z_i) (.) alpha_hat_i) over the signers with skip[i] == 0

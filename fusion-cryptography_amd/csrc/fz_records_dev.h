@@ -3,7 +3,8 @@
 // and the aggregation straight from the bytes, of one committee and of many; fz_verify_encoded.hip:
 // the verification straight from the bytes; fz_sign_encoded.hip: signing straight to the bytes; fz_sign_records.hip: signing
 // straight from the key's bytes to the signature's; fz_keygen_records.hip: key generation straight to the key's bytes, which
-// takes the field packing, the range check's step and the status flag): the packed chunk of the chunk
+// takes the field packing, the range check's step and the status flag; fz_vk_records.hip: the verification key straight from the
+// key's bytes, on the consumers' steps): the packed chunk of the chunk
 // walk with its loads and stores, the field packing and unpacking, the consumers' steps from the packed chunk to the transform's
 // outputs and their sums, the per-record status flag, the record walk, the chunk walk's opening, and the producers' steps from
 // the int32 image to the stored chunk (the range check's operands and its per-value step, the inverse transform centred into the

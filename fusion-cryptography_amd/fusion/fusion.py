@@ -637,6 +637,31 @@ def sign_from_bytes(params: Params, secret_record: bytes, vk: OneTimeVerificatio
     return data.tobytes()
 
 
+def vk_of_secret_bytes(params: Params, secret_record: bytes) -> OneTimeVerificationKey:
+    """NOT in the reference: the verification key of one "secret" record, keygen(params, seed)[1] for the record
+    keygen_to_bytes(params, seed) returned, without the key's rows in between -- one fz_vk_records_async call that unpacks the
+    record, transforms it and multiplies by the public challenge.  Raises ValueError for a record of the wrong length, and
+    with the reason for a record that is not canonical (6)."""
+    from fusion_hip import ENCODING_REASONS
+    from fusion_hip.scheme import encoded_size
+    size = encoded_size(params, "secret")
+    if len(secret_record) != size:
+        raise ValueError(f"a 'secret' record is {size} bytes, not {len(secret_record)}")
+    vk, codes = _ctx(params).vk_records(bytes(secret_record), int(params.beta_sk), _rows_of(params.public_challenge, params.modulus),
+                                        params.num_rows_sk)
+    if codes[0]:
+        raise ValueError(ENCODING_REASONS[int(codes[0])])
+    return OneTimeVerificationKey(left_vk_hat=_column(params, vk[0, 0:1]), right_vk_hat=_column(params, vk[0, 1:2]))
+
+
+def sign_from_secret_bytes(params: Params, secret_record: bytes, message: str) -> Tuple[bytes, OneTimeVerificationKey]:
+    """NOT in the reference: sign_from_bytes from the record alone -> (the signature's bytes, the verification key the record
+    belongs to): vk_of_secret_bytes, then sign_from_bytes with that key -- the challenge through hash_ch, whoever stands behind
+    that name.  Raises ValueError as those two do."""
+    vk = vk_of_secret_bytes(params, secret_record)
+    return sign_from_bytes(params, secret_record, vk, message), vk
+
+
 def from_bytes(params: Params, kind: str, data: bytes):
     """NOT in the reference: the inverse of to_bytes for one record of `kind` ("vk", "signature", "aggregate" or "secret") -> a
     OneTimeVerificationKey, a Signature or a OneTimeSigningKey (seed=None: the record does not hold it).  Raises ValueError for

@@ -114,6 +114,7 @@ SIGNATURES = {
     "fz_sign_encoded_async": (c_int, [_ctx, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_void_p, c_void_p]),
     "fz_sign_records_async": (c_int, [_ctx, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int64, c_void_p, c_void_p]),
     "fz_keygen_records_async": (c_int, [_ctx, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "fz_vk_records_async": (c_int, [_ctx, c_void_p, c_void_p, c_int64, c_size_t, c_int, c_void_p, c_void_p]),
     "fz_check_records_async": (c_int, [_ctx, c_void_p, c_size_t, c_int, c_int64, c_void_p]),
     "fz_aggregate_encoded_async": (c_int, [_ctx, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_void_p, c_void_p]),
     "fz_aggregate_encoded_ragged_async": (c_int, [_ctx, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_size_t, c_int, c_int64,

@@ -430,6 +430,14 @@ class Context:
         check(self._lib, self._lib.fz_keygen_records_async(self._h, c_void_p(d_A), c_void_p(d_coef), coef_rows, n, l, key_bound,
                                                            c_void_p(d_bytes), c_void_p(d_vk), c_void_p(d_status)))
 
+    def vk_records_async_dev(self, d_A, d_key_bytes, key_bound, n, l, d_vk, d_status):
+        """the verification keys straight from the keys' bytes: d_key_bytes holds n "secret" records ([2][l][d] fields s + key_bound,
+        left half first); d_vk [n][2][d] = per half cent(sum_k cent(NTT(s_k) (.) A_k)), exactly what keygen_records_async_dev wrote
+        beside the records and what decode_records_async_dev(rows = 2 l, coef) followed by matvec leaves, without the int32
+        rows; codes (0, 6: a key field above 2 key_bound) to d_status [n], a refused key's vk zero (asynchronous)"""
+        check(self._lib, self._lib.fz_vk_records_async(self._h, c_void_p(d_A), c_void_p(d_key_bytes), key_bound, n, l, c_void_p(d_vk),
+                                                       c_void_p(d_status)))
+
     def decode_records_async_dev(self, d_bytes, n, rows, coef, bound, d_rows, d_status):
         """... and back: codes (0, 6) to d_status [n], a refused record's rows zero (asynchronous)"""
         check(self._lib, self._lib.fz_decode_records_async(self._h, c_void_p(d_bytes), n, rows, 1 if coef else 0, bound,
@@ -643,6 +651,27 @@ class Context:
             dB, dK, dV = self._scratch(s, max(1, batch * kb)), self._scratch(s, max(1, batch * 2 * d * 4)), self._scratch(s, max(1, batch * 4))
             self.keygen_records_async_dev(dA.ptr, dC.ptr, coef_rows, batch, l, int(key_bound), dB.ptr, dK.ptr, dV.ptr)
             return dB.to_numpy(np.uint8, (batch, kb)), dK.to_numpy(np.int32, (batch, 2, d)), dV.to_numpy(np.int32, (batch,))
+
+    def vk_records(self, key_bytes, key_bound, A, l):
+        """key_bytes: "secret" records of [2][l][d] fields under key_bound (uint8, [batch][2 * l * d * wk / 8] or flat; the count
+        is taken from the length); A [l][d] -> (vk int32 [batch][2][d], codes int32 [batch]): the verification keys of the
+        records in one pass (vk_records_async_dev), codes 0 or 6, a refused key's vk zero."""
+        A, l = _as_i32(A), int(l)
+        if A.ndim != 2 or A.shape[0] != l:
+            raise FusionHipError(FZ_E_BADARG, f"A of shape {A.shape}: [{l}][d] expected")
+        d = A.shape[1]
+        kb = 2 * l * d * (2 * int(key_bound)).bit_length() // 8
+        key = np.ascontiguousarray(np.frombuffer(key_bytes, dtype=np.uint8) if isinstance(key_bytes, (bytes, bytearray, memoryview))
+                                   else key_bytes)
+        if key.dtype != np.uint8 or kb == 0 or key.size % kb:
+            raise FusionHipError(FZ_E_BADARG, f"{key.size} bytes of {key.dtype}: whole uint8 records of {kb} bytes expected")
+        batch = key.size // kb
+        with DeviceScope() as s:
+            dA, = self._staged(s, [A])
+            dK = s.own(DeviceBuffer.from_numpy(self, key.reshape(batch, kb))) if batch else self._scratch(s, 1)
+            dV, dS = self._scratch(s, max(1, batch * 2 * d * 4)), self._scratch(s, max(1, batch * 4))
+            self.vk_records_async_dev(dA.ptr, dK.ptr, int(key_bound), batch, l, dV.ptr, dS.ptr)
+            return dV.to_numpy(np.int32, (batch, 2, d)), dS.to_numpy(np.int32, (batch,))
 
     def _sign_bytes(self, c, l, bound, key_dev, launch):
         """the tail sign_encoded and sign_records share, c = c_hat [batch][d]: in one DeviceScope the key (key_dev(scope)) and the

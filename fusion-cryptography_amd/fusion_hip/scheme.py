@@ -359,6 +359,79 @@ class BatchScheme:
         return self._sign_to_bytes(n, "secret records", vk, messages, device, lambda s: self._records_dev(s, secret, n, kb),
                                    lambda dK, dC, bound, dB, dV: self.ctx.sign_records_async_dev(dK, key_bound, dC, n, self.l, bound, dB, dV))
 
+    def _vk_of_records(self, s, dK, n):
+        """the verification keys of the n "secret" records dK holds on the device, in one pass (vk_records_async_dev): -> (a
+        DeviceArray [n][2][d] of the scope `s`, codes int32 [n] on the host: 0, or 6 with the key's vk zero)"""
+        key_bound = _encoding(self.params, "secret")[2]
+        dV, dS = self._new(s, (n, 2, self.d)), self._new(s, (n,))
+        self.ctx.vk_records_async_dev(self._A_dev().ptr, dK.ptr, key_bound, n, self.l, dV.ptr, dS.ptr)
+        return dV, dS.numpy()
+
+    def vk_from_records(self, secret, device=False):
+        """the verification keys of N "secret" records (`secret` in every form decode takes) -> (vk
+        [N][2][d], codes int32 [N]): vk[i] is bit for bit the key keygen_batch_encoded returned beside record i, and
+        matvec(A, decode("secret", secret)[0]) for any canonical record.  vk is a numpy array, or with device=True a DeviceArray
+        that challenges_dev / sign_batch_records take as it is; codes are on the host: codes[i] is 6 (ENCODING_REASONS) when
+        record i is not canonical (a field above 2 beta_sk), and vk[i] is then zero.  One fused pass unpacks, range-checks and
+        transforms the key and multiplies by the public challenge: the int32 key [N][2][l][d] -- 4.57 times the record -- never
+        exists on the device.
+        A length that is not N whole records raises FusionHipError(FZ_E_BADARG) before the device is touched.  N == 0 returns
+        empty numpy arrays for either value of `device`, as sign_batch_records does."""
+        kb = _encoding(self.params, "secret")[4]
+        secret, n = _records_input("secret", secret, kb)
+        if n == 0:
+            return np.zeros((0, 2, self.d), dtype=np.int32), np.zeros(0, dtype=np.int32)
+        with DeviceScope() as s:
+            dV, codes = self._vk_of_records(s, self._records_dev(s, secret, n, kb), n)
+            return (s.release(dV) if device else dV.numpy()), codes
+
+    def sign_batch_secret(self, secret, messages, device=False):
+        """sign_batch_records from the records alone: -> (data uint8 [N][encoded_size(params, "signature")], codes int32 [N], vk
+        [N][2][d] int32).  The keys are derived on the device (vk_from_records' pass), sign_batch's challenge pass reads them
+        where they are -- no key is uploaded -- and one sign_records_async_dev launch signs; for canonical records data and
+        codes are bit for bit sign_batch_records(secret, vk, messages).  data is a numpy array, or with device=True a uint8
+        DeviceArray; codes and vk are on the host (aggregate needs the keys there).  A record with code 6 signs nothing: its
+        bytes are zero, and so is its vk.
+        A length that is not N whole records, or a number of messages other than N, raises FusionHipError(FZ_E_BADARG) before
+        the device is touched.  N == 0 returns empty numpy arrays for either value of `device`."""
+        _, _, key_bound, _, kb = _encoding(self.params, "secret")
+        _, _, bound, _, rb = _encoding(self.params, "signature")
+        secret, n = _records_input("secret", secret, kb)
+        if len(messages) != n:
+            raise FusionHipError(FZ_E_BADARG, f"{len(messages)} messages, {n} secret records")
+        if n == 0:
+            return np.zeros((0, rb), dtype=np.uint8), np.zeros(0, dtype=np.int32), np.zeros((0, 2, self.d), dtype=np.int32)
+        with DeviceScope() as s:
+            dK = self._records_dev(s, secret, n, kb)
+            dV = self._vk_of_records(s, dK, n)[0]           # (a record refused here is refused by the signing pass too)
+            dC = self._challenges_both(dV, messages, want_host=False, scope=s)[0]
+            dB, dS = self._new(s, (n, rb), np.uint8), self._new(s, (n,))
+            self.ctx.sign_records_async_dev(dK.ptr, key_bound, dC.ptr, n, self.l, bound, dB.ptr, dS.ptr)
+            codes, vk = dS.numpy(), dV.numpy()
+            return (s.release(dB) if device else dB.numpy()), codes, vk
+
+    def check_keypairs(self, secret, vk):
+        """does "secret" record i belong to vk[i]?  -> codes int32 [N]: 0 when the record is canonical and its derived key
+        (vk_from_records) equals vk[i] mod q, 3 (VERDICT_REASONS: the target mismatch) when it does not, 6 (ENCODING_REASONS)
+        when the record is not canonical.  vk [N][2][d]: a numpy array or a DeviceArray, any residues.  The keys are derived
+        on the device and compared on the host (2 KiB per key).
+        A length that is not N whole records, or a number of keys other than N, raises FusionHipError(FZ_E_BADARG) before
+        the device is touched."""
+        kb = _encoding(self.params, "secret")[4]
+        secret, n = _records_input("secret", secret, kb)
+        try:
+            nk = self._signer_count(vk)
+        except ValueError:
+            nk = -1
+        if nk != n:
+            raise FusionHipError(FZ_E_BADARG, f"{nk} keys, {n} secret records")
+        if n == 0:
+            return np.zeros(0, dtype=np.int32)
+        derived, codes = self.vk_from_records(secret)
+        want = self._split_vk(vk)[0]
+        same = ((derived.astype(np.int64) - want.astype(np.int64)) % self.q == 0).all(axis=(1, 2))
+        return np.where(codes != 0, codes, np.where(same, 0, 3)).astype(np.int32)
+
     def _sign_to_bytes(self, n, keys_are, vk, messages, device, key_dev, launch):
         """what sign_batch_encoded and sign_batch_records share once the key's own checks gave its N = n (`keys_are`: what n counts,
         for the message): the count check, the empty answer, and in one DeviceScope the challenges, the key on the device

@@ -383,6 +383,25 @@ FZ_API int fz_sign_records_async(fz_ctx *ctx, const uint8_t *d_key_bytes, int64_
 FZ_API int fz_keygen_records_async(fz_ctx *ctx, const int32_t *d_A, const int32_t *d_coef, int coef_rows, size_t N, int l,
                                    int64_t key_bound, uint8_t *d_key_bytes, int32_t *d_vk, int *d_status);
 
+/* the verification keys of N "secret" records straight from their bytes (fusion/fusion.py:363-370 read backwards: the public key
+ * from the private one; no int32 row of the key reaches memory).  d_key_bytes holds the records in the format fz_sign_records_async
+ * reads and fz_keygen_records_async writes: [2][l][degree] fields u of wk = bit_length(2 * key_bound) bits, left half first.
+ * d_A [l][degree] is the public challenge, any int32.  With s = u - key_bound and FWD the context's forward transform,
+ *     d_vk[b][h][j] = cent(sum over k < l of cent(FWD(s[b][h][k])[j] * A[k][j]))        for h = 0, 1
+ * -- the sums are exact.  For records fz_keygen_records_async wrote this is bit for bit the d_vk it wrote beside them; for any
+ * canonical record it is what fz_decode_records_async(rows = 2 l, coef = 1, key_bound) followed by fz_matvec over the 2 N halves
+ * leaves.  d_status[b] = FZ_VERDICT_ENCODING when some field of record b, in either half, is above 2 * key_bound, else 0; a
+ * refused key's d_vk[b] is all zero (both halves), the others are unaffected.  The key bytes and d_A are not written, and nothing
+ * beyond d_vk[N - 1] and d_status[N - 1] is.  Rules of fz_sign_records_async, in its order: FZ_E_BADARG for a NULL context,
+ * l < 1 or key_bound outside [1, (q-1)/2]; N == 0 does nothing and writes nothing; FZ_E_BADARG for a pointer that is NULL or not
+ * 16-byte aligned (all four, NULL before misaligned); FZ_E_UNSUPPORTED for degrees other than 64 and 256; FZ_E_BADARG for N
+ * records of 2 l rows that are too many (2 * l * degree > 2^31 - 1, or more than 2^61 values in all); then the entry's own limits:
+ * FZ_E_BADARG for N > 0x3fffffff (a workgroup per (key, half) in one grid) and FZ_E_UNSUPPORTED for l >= 2^22 (exact fp64 sums).
+ * Asynchronous on the context's stream, allocation-free, capturable by fz_graph_* on a context's first call too (the clear of
+ * d_status and the zeroing of refused keys are part of the captured work). */
+FZ_API int fz_vk_records_async(fz_ctx *ctx, const int32_t *d_A, const uint8_t *d_key_bytes, int64_t key_bound, size_t N, int l,
+                               int32_t *d_vk, int *d_status);
+
 /* the range check of fz_decode_records_async alone (no transform, no rows): status per record 0 or FZ_VERDICT_ENCODING (a field
  * > 2 * bound); nothing else is written.  Same arguments and rules as fz_decode_records_async, for either kind of record. */
 FZ_API int fz_check_records_async(fz_ctx *ctx, const uint8_t *d_bytes, size_t n, int rows, int64_t bound, int *d_status);
