@@ -75,13 +75,7 @@ __device__ __forceinline__ void agg_fold(double (&lo)[R][4], double (&hi)[R][4],
             hi[r][k] = 0.0;
         }
 }
-// one int4 column of the verification target: acc += (L * c + R) * alpha, the inner value |L * c mod q + R| < 2^32
-__device__ __forceinline__ void agg_target4(int4 L, int4 R, int4 ch, int4 a, double (&acc)[4], FzMod m) {
-    acc[0] += fz_mulmod(fz_mulmod((double)L.x, (double)ch.x, m) + (double)R.x, (double)a.x, m);
-    acc[1] += fz_mulmod(fz_mulmod((double)L.y, (double)ch.y, m) + (double)R.y, (double)a.y, m);
-    acc[2] += fz_mulmod(fz_mulmod((double)L.z, (double)ch.z, m) + (double)R.z, (double)a.z, m);
-    acc[3] += fz_mulmod(fz_mulmod((double)L.w, (double)ch.w, m) + (double)R.w, (double)a.w, m);
-}
+// (the term of the verification target, agg_target4: fz_stream_dev.h)
 
 // RAG = FzNoRag: `groups` aggregates of N signers each, aggregate g's rows at g * N; RAG = FzRagged: aggregates of DIFFERENT
 // sizes in one launch (fz_aggregate_*_ragged: many independent aggregate() calls, fusion.py:655, batched) -- aggregate g's

@@ -1,7 +1,8 @@
 // fz_aggregate_encoded_dev.h -- the body the two aggregations straight from the bytes share (fz_aggregate_encoded.hip: one
 // committee per launch; fz_aggregate_many_encoded.hip: many committees of different sizes per launch): one workgroup's walk over
-// one slice of signers for one chunk column, from the first prefetch to the atomics of the epilogue.  No kernels and no host code
-// here; private to the unit that includes it.
+// one slice of signers for one chunk column, from the first prefetch to the atomics of the epilogue; and what the launches of many
+// committees share (fz_aggregate_many_encoded.hip, fz_aggregate_target_encoded.hip): the launch's slice count and group table, the clearing of the partials and their centring.  No kernels here;
+// private to the unit that includes it.
 #ifndef FZ_AGGREGATE_ENCODED_DEV_H
 #define FZ_AGGREGATE_ENCODED_DEV_H
 
@@ -102,6 +103,57 @@ __device__ __forceinline__ void aggregate_encoded_slice(double *lds, const uint8
         for (int v = 0; v < kWavesPerBlock; ++v) sum += lds[v * REGION + pad16((int)e)];
         if (e < valid) atomicAdd(dst + e, (unsigned long long)(long long)sum);
     }
+}
+
+// ---- many committees per launch: grid (.., slices, groups), host code ----
+
+// The slice count of the launch of groups [0, groups) of h_offsets (at most kFzRaggedMax) on `columns` chunk columns, for a kernel
+// of resident grid `grid`, and the launch's group table; -> 0 when every group is empty (nothing to launch):
+// * one round: when columns x groups divides the kernel's resident grid well -- floor(grid / (columns x groups)) slices fill at
+//   least 7/8 of it -- that many slices, as aggregate_encoded chooses them: every workgroup is resident from the first moment and
+//   none waits for a second round (one group of 1024 signers at secpar 256: 56 us so, 67-69 us with two or four times as many);
+// * several rounds of short workgroups otherwise -- a badly filled grid (16 groups x 21 columns = 336 of 512) or more columns x
+//   groups than the grid holds, where the groups' sizes decide how long the last workgroup runs -- about four times the
+//   resident grid, but no slices of fewer than 16 signers of the largest group (a wave needs a few signers for its prefetch to
+//   pay the workgroup's prologue): 16 x 256 signers 279 -> 211 us, 70 groups of 1 .. 194 signers 390 -> 352 us.
+// Never more slices than give every wave of a workgroup of the LARGEST group a signer, never above the grid limit.  The figures:
+// DESIGN.md section 5.16, profiles/r16_aggregate_many_encoded.txt.
+inline size_t ragged_slices(size_t grid, size_t columns, const size_t *h_offsets, size_t groups, FzRagged &rag) {
+    size_t nmax = 0;
+    for (size_t g = 0; g < groups; ++g) nmax = nmax < h_offsets[g + 1] - h_offsets[g] ? h_offsets[g + 1] - h_offsets[g] : nmax;
+    if (nmax == 0) return 0;
+    const size_t cg = columns * groups;
+    size_t slices = grid / cg, cap = (nmax + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (slices < 1 || 8 * slices * cg < 7 * grid) {
+        slices = (4 * grid + cg - 1) / cg;
+        cap = (nmax + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock);
+    }
+    slices = slices < cap ? slices : cap;
+    slices = slices < 65535 ? slices : 65535;
+    for (size_t g = 0; g < groups; ++g) {                 // as fill_ragged (fz_aggregate.hip)
+        const size_t ng = h_offsets[g + 1] - h_offsets[g];
+        rag.off[g] = (unsigned)h_offsets[g];
+        rag.base[g] = (unsigned)(ng / slices);
+        rag.extra[g] = (unsigned)(ng % slices);
+    }
+    rag.off[groups] = (unsigned)h_offsets[groups];
+    return slices;
+}
+
+// `groups` partials of `width` int64, `stride` apart, zeroed: theirs alone, the words between two partials are not touched
+inline int partials_clear(fz_ctx *ctx, int64_t *d_partial, size_t stride, size_t width, size_t groups, const char *what) {
+    if (stride == width || groups == 1)
+        return fz_check_hip(hipMemsetAsync(d_partial, 0, groups * width * sizeof(int64_t), ctx->stream), what);
+    return fz_check_hip(hipMemset2DAsync(d_partial, stride * sizeof(int64_t), 0, width * sizeof(int64_t), groups, ctx->stream), what);
+}
+
+// d_out [groups][width] = cent() of the partials (fz_reduce_i64's kernel: one launch over all groups when the partials are
+// contiguous, one per group otherwise)
+inline int partials_cent(fz_ctx *ctx, const int64_t *d_partial, size_t stride, size_t width, size_t groups, int32_t *d_out) {
+    if (stride == width || groups == 1) return fz_launch_reduce_i64(ctx, d_partial, d_out, groups * width);
+    int rc = FZ_OK;
+    for (size_t g = 0; rc == FZ_OK && g < groups; ++g) rc = fz_launch_reduce_i64(ctx, d_partial + g * stride, d_out + g * width, width);
+    return rc;
 }
 
 }  // namespace

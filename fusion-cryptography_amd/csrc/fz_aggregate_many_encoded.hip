@@ -37,38 +37,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void aggregate_encoded_ragged(
                                         partial + (size_t)g * pstride, twB, tab, m);
 }
 
-// the launch of groups [0, groups) of h_offsets (at most kFzRaggedMax).  The slice count is the launch's:
-// * one round: when columns x groups divides the kernel's resident grid well -- floor(grid / (columns x groups)) slices fill at
-//   least 7/8 of it -- that many slices, as aggregate_encoded chooses them: every workgroup is resident from the first moment and
-//   none waits for a second round (one group of 1024 signers at secpar 256: 56 us so, 67-69 us with two or four times as many);
-// * several rounds of short workgroups otherwise -- a badly filled grid (16 groups x 21 columns = 336 of 512) or more columns x
-//   groups than the grid holds, where the groups' sizes decide how long the last workgroup runs -- about four times the
-//   resident grid, but no slices of fewer than 16 signers of the largest group (a wave needs a few signers for its prefetch to
-//   pay the workgroup's prologue): 16 x 256 signers 279 -> 211 us, 70 groups of 1 .. 194 signers 390 -> 352 us.
-// Never more slices than give every wave of a workgroup of the LARGEST group a signer, never above the grid limit.  The figures:
-// DESIGN.md section 5.16, profiles/r16_aggregate_many_encoded.txt.
+// the launch of groups [0, groups) of h_offsets (at most kFzRaggedMax); the slice count is the launch's (ragged_slices)
 template <int LOGD, bool FAST>
 int launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const size_t *h_offsets,
                                     size_t groups, unsigned rv, unsigned rb, int w, int bound, int64_t *partial, size_t pstride) {
-    size_t nmax = 0;
-    for (size_t g = 0; g < groups; ++g) nmax = nmax < h_offsets[g + 1] - h_offsets[g] ? h_offsets[g + 1] - h_offsets[g] : nmax;
-    if (nmax == 0) return FZ_OK;                          // nobody adds to these partials: they stay as the entry cleared them
-    const size_t columns = (rv + kChunk - 1) / kChunk, cg = columns * groups, grid = (size_t)ctx->grid_aggenc_rag;
-    size_t slices = grid / cg, cap = (nmax + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (slices < 1 || 8 * slices * cg < 7 * grid) {
-        slices = (4 * grid + cg - 1) / cg;
-        cap = (nmax + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock);
-    }
-    slices = slices < cap ? slices : cap;
-    slices = slices < 65535 ? slices : 65535;
     FzRagged rag;
-    for (size_t g = 0; g < groups; ++g) {                 // as fill_ragged (fz_aggregate.hip)
-        const size_t ng = h_offsets[g + 1] - h_offsets[g];
-        rag.off[g] = (unsigned)h_offsets[g];
-        rag.base[g] = (unsigned)(ng / slices);
-        rag.extra[g] = (unsigned)(ng % slices);
-    }
-    rag.off[groups] = (unsigned)h_offsets[groups];
+    const size_t columns = (rv + kChunk - 1) / kChunk;
+    const size_t slices = ragged_slices((size_t)ctx->grid_aggenc_rag, columns, h_offsets, groups, rag);
+    if (slices == 0) return FZ_OK;                        // nobody adds to these partials: they stay as the entry cleared them
     hipLaunchKernelGGL((aggregate_encoded_ragged<LOGD, FAST>), dim3((unsigned)columns, (unsigned)slices, (unsigned)groups),
                        dim3(64 * kWavesPerBlock), 0, ctx->stream, bytes, alpha, skip, rag, rv, rb, w, bound, (unsigned long long *)partial,
                        pstride, (const double2 *)ctx->d_twB, (const FzTwA *)ctx->d_twAB, ctx->mod);
@@ -92,12 +68,7 @@ int fz_aggregate_many_encoded_query_grid(fz_ctx *ctx) {
 int fz_launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const size_t *h_offsets,
                                        size_t groups, int l, int w, int64_t bound, int64_t *d_partial, size_t pstride, int32_t *d_out) {
     const unsigned rv = (unsigned)l * (unsigned)ctx->degree, rb = (unsigned)fz_record_bytes(ctx->degree, l, w);
-    int rc;
-    if (pstride == rv || groups == 1)
-        rc = fz_check_hip(hipMemsetAsync(d_partial, 0, groups * (size_t)rv * sizeof(int64_t), ctx->stream), "aggregate partials clear");
-    else
-        rc = fz_check_hip(hipMemset2DAsync(d_partial, pstride * sizeof(int64_t), 0, (size_t)rv * sizeof(int64_t), groups, ctx->stream),
-                          "aggregate partials clear");
+    int rc = partials_clear(ctx, d_partial, pstride, rv, groups, "aggregate partials clear");
     for (size_t g0 = 0; rc == FZ_OK && g0 < groups; g0 += (size_t)kFzRaggedMax) {
         const size_t n = groups - g0 < (size_t)kFzRaggedMax ? groups - g0 : (size_t)kFzRaggedMax;
         rc = fz_dispatch<6, 8>(ctx, FZ_E_UNSUPPORTED, [&](auto logd, auto fast) {
@@ -106,7 +77,5 @@ int fz_launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const 
         });
     }
     if (rc != FZ_OK || d_out == nullptr) return rc;
-    if (pstride == rv || groups == 1) return fz_launch_reduce_i64(ctx, d_partial, d_out, groups * (size_t)rv);
-    for (size_t g = 0; rc == FZ_OK && g < groups; ++g) rc = fz_launch_reduce_i64(ctx, d_partial + g * pstride, d_out + g * (size_t)rv, rv);
-    return rc;
+    return partials_cent(ctx, d_partial, pstride, rv, groups, d_out);
 }

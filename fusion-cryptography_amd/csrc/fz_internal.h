@@ -358,6 +358,14 @@ int fz_launch_aggregate_encoded(fz_ctx *ctx, const uint8_t *bytes, const int32_t
 int fz_launch_aggregate_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const size_t *h_offsets,
                                        size_t groups, int l, int w, int64_t bound, int64_t *d_partial, size_t pstride, int32_t *d_out);
 
+// the same with the groups' verification targets beside the aggregates (fz_aggregate_target_encoded.hip; degree 64 / 256): the
+// int64 partial [degree] at d_target_partial + g * tstride is zeroed, then summed over group g's signers with skip[i] == 0 as
+// fz_launch_aggregate sums it with tout64 (the term of agg_target4) from vk [N][2][degree] and chal [N][degree]; one launch per
+// kFzRaggedMax groups for both kinds of sums.  d_partial, pstride and d_out as above.
+int fz_launch_aggregate_target_encoded_ragged(fz_ctx *ctx, const uint8_t *bytes, const int32_t *alpha, const int *skip, const int32_t *vk,
+                                              const int32_t *chal, const size_t *h_offsets, size_t groups, int l, int w, int64_t bound,
+                                              int64_t *d_partial, size_t pstride, int64_t *d_target_partial, size_t tstride, int32_t *d_out);
+
 // verification straight from the bytes (fz_verify_encoded.hip; degree 64 / 256): d_verdict [N] = 0, FZ_VERDICT_TARGET_MISMATCH or
 // FZ_VERDICT_ENCODING of N records of l rows against `target` [N][degree] (any residues) or, when vk != NULL, against
 // cent(vkL (.) c + vkR) from vk [N][2][degree] and chal [N][degree].  Records are multiples of 16 bytes.

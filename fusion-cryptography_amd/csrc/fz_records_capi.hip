@@ -3,14 +3,7 @@
 // argument rules the entries share (fz_records_args.h), and per entry what is its own; the kernels and their launchers are the units
 // fz_records.hip, fz_sign_encoded.hip, fz_sign_records.hip, fz_keygen_records.hip, fz_aggregate_encoded.hip,
 // fz_aggregate_many_encoded.hip and fz_verify_encoded.hip.
-#include "fz_records_args.h"      // records_bound, records_args, records_ptrs: shared with fz_key_records_capi.hip
-
-// the consumers that walk ONE record's chunks (blockIdx names the record): every record must begin on a 16-byte unit
-static int records_whole_units(const fz_ctx *ctx, int rows, int w) {
-    const size_t rb = fz_record_bytes(ctx->degree, rows, w);
-    if (rb % 16 != 0) return fz_set_error(FZ_E_UNSUPPORTED, "records of %zu bytes: reading them record by record needs a multiple of 16", rb);
-    return FZ_OK;
-}
+#include "fz_records_args.h"      // records_bound, records_args, records_ptrs, records_whole_units, records_ragged_args: shared
 
 extern "C" {
 
@@ -99,28 +92,13 @@ int fz_aggregate_encoded_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_
 }
 
 // many committees in one launch: group g owns records [h_offsets[g], h_offsets[g + 1]).  The argument rules are
-// fz_aggregate_encoded_async's, in its order, then the offsets and the stride.
+// fz_aggregate_encoded_async's, in its order, then the offsets and the stride (records_ragged_args).
 int fz_aggregate_encoded_ragged_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
                                       const size_t *h_offsets, size_t groups, int l, int64_t bound, int64_t *d_partial,
                                       size_t partial_stride, int32_t *d_out) {
     int w = 0;
-    FZ_REQUIRE(groups == 0 || h_offsets, "NULL argument");
-    const size_t total = groups ? h_offsets[groups] : 0;
-    FZ_REQUIRE(total == 0 || d_alpha_hat, "NULL argument");
-    FZ_REQUIRE((((uintptr_t)d_alpha_hat | (uintptr_t)d_out) & 15) == 0, "alpha_hat and the aggregates must be 16-byte aligned");
-    // (a call whose groups are all empty reads no byte: the stream may be NULL then)
-    FZ_TRY(records_args(ctx, groups == 0 ? 0 : (total ? total : 1), l, bound,
-                        total ? records_ptrs(d_bytes, d_partial, d_alpha_hat) : records_ptrs(d_partial), &w));
+    FZ_TRY(records_ragged_args(ctx, d_bytes, d_alpha_hat, h_offsets, groups, l, bound, d_partial, partial_stride, d_out, &w));
     if (groups == 0) return FZ_OK;
-    FZ_TRY(records_whole_units(ctx, l, w));
-    for (size_t g = 0; g < groups; ++g) FZ_REQUIRE(h_offsets[g] <= h_offsets[g + 1], "offsets must not decrease");
-    FZ_REQUIRE(groups == 1 || (partial_stride >= (size_t)l * ctx->degree && (partial_stride & 1) == 0),
-               "partial_stride must be at least l * degree, and even (16-byte aligned partials)");
-    for (size_t g = 0; g < groups; ++g)
-        if (h_offsets[g + 1] - h_offsets[g] >= ((size_t)1 << 22))
-            return fz_set_error(FZ_E_UNSUPPORTED, "group %zu: %zu signers are too many for exact fp64 accumulation (< 2^22)", g,
-                                h_offsets[g + 1] - h_offsets[g]);
-    if (total >= 0xffffffc0ull) return fz_set_error(FZ_E_UNSUPPORTED, "%zu records in one call: signer indices are 32-bit", total);
     FZ_DEV(ctx);
     return fz_launch_aggregate_encoded_ragged(ctx, d_bytes, d_alpha_hat, d_skip, h_offsets, groups, l, w, bound, d_partial, partial_stride,
                                               d_out);

@@ -1,5 +1,6 @@
-// fz_stream_dev.h -- what the two units of streaming kernels share (fz_pointwise.hip, fz_aggregate.hip): the workgroup size, the
-// centring to int32, the streaming 16-byte accesses and the grid of a flat launch.  No kernels here; everything is private to the
+// fz_stream_dev.h -- what the units of streaming kernels share (fz_pointwise.hip, fz_aggregate.hip): the workgroup size, the
+// centring to int32, the streaming 16-byte accesses, the grid of a flat launch, and the term of the verification target, which
+// fz_aggregate_target_encoded.hip forms as fz_aggregate.hip does.  No kernels here; everything is private to the
 // unit that includes it.
 #ifndef FZ_STREAM_DEV_H
 #define FZ_STREAM_DEV_H
@@ -21,6 +22,14 @@ __device__ __forceinline__ int4 ld_stream4(const int4 *p) {
 __device__ __forceinline__ void st_stream4(int4 *p, const int4 &v) {
     const fz_v4i t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<fz_v4i *>(p));
+}
+
+// one int4 column of the verification target: acc += (L * c + R) * alpha, the inner value |L * c mod q + R| < 2^32
+__device__ __forceinline__ void agg_target4(int4 L, int4 R, int4 ch, int4 a, double (&acc)[4], FzMod m) {
+    acc[0] += fz_mulmod(fz_mulmod((double)L.x, (double)ch.x, m) + (double)R.x, (double)a.x, m);
+    acc[1] += fz_mulmod(fz_mulmod((double)L.y, (double)ch.y, m) + (double)R.y, (double)a.y, m);
+    acc[2] += fz_mulmod(fz_mulmod((double)L.z, (double)ch.z, m) + (double)R.z, (double)a.z, m);
+    acc[3] += fz_mulmod(fz_mulmod((double)L.w, (double)ch.w, m) + (double)R.w, (double)a.w, m);
 }
 
 unsigned grid_for(fz_ctx *ctx, size_t work_items, int per_cu = -1) {

@@ -683,14 +683,8 @@ def from_bytes(params: Params, kind: str, data: bytes):
     return vk_to_object(params, rows[0]) if kind == "vk" else signature_to_object(params, rows[0])
 
 
-def aggregate_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
-                         blobs: List[bytes]) -> Signature:
-    """NOT in the reference: aggregate() of signatures given as their compact bytes (one "signature" record of to_bytes
-    each), without ever expanding them -- the Signature that aggregate(params, keys, messages, [from_bytes(params,
-    "signature", b) for b in blobs]) returns (BatchScheme.aggregate_encoded: one fused pass over the bytes).  Raises
-    ValueError for unequal numbers of keys, messages and blobs, for a blob of the wrong length, and for a record that is not
-    canonical (with the index of the first one and the reason).  The target equation of a signature is NOT checked, as
-    aggregate() does not check it either: verify() the result."""
+def _aggregate_from_bytes(params, keys, messages, blobs, verify):
+    """aggregate_from_bytes (verify=False: no verdict, None) and aggregate_verify_from_bytes: -> (Signature, verdict)"""
     from fusion_hip import ENCODING_REASONS
     from fusion_hip.scheme import BatchScheme, encoded_size, vk_from_object
     if not (len(keys) == len(messages) == len(blobs)):
@@ -704,13 +698,34 @@ def aggregate_from_bytes(params: Params, keys: List[OneTimeVerificationKey], mes
     vk = np.stack([vk_from_object(params, k) for k in keys])
     bs = BatchScheme(params)
     try:
-        out, codes = bs.aggregate_encoded(vk, list(messages), b"".join(bytes(b) for b in blobs))
+        call = bs.aggregate_verify_encoded if verify else bs.aggregate_encoded
+        out, codes, *verdict = call(vk, list(messages), b"".join(bytes(b) for b in blobs))
     finally:
         bs.close()
     bad = np.flatnonzero(codes)
     if bad.size:
         raise ValueError(f"record {int(bad[0])}: {ENCODING_REASONS[int(codes[bad[0]])]}")
-    return Signature(signature_hat=_column(params, out))
+    return Signature(signature_hat=_column(params, out)), (verdict[0] if verify else None)
+
+
+def aggregate_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
+                         blobs: List[bytes]) -> Signature:
+    """NOT in the reference: aggregate() of signatures given as their compact bytes (one "signature" record of to_bytes
+    each), without ever expanding them -- the Signature that aggregate(params, keys, messages, [from_bytes(params,
+    "signature", b) for b in blobs]) returns (BatchScheme.aggregate_encoded: one fused pass over the bytes).  Raises
+    ValueError for unequal numbers of keys, messages and blobs, for a blob of the wrong length, and for a record that is not
+    canonical (with the index of the first one and the reason).  The target equation of a signature is NOT checked, as
+    aggregate() does not check it either: verify() the result, or call aggregate_verify_from_bytes."""
+    return _aggregate_from_bytes(params, keys, messages, blobs, False)[0]
+
+
+def aggregate_verify_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
+                                blobs: List[bytes]) -> Tuple[Signature, Tuple[bool, str]]:
+    """NOT in the reference: aggregate_from_bytes and verify() of its result in one pass, as an aggregator that checks its own
+    output does -> (Signature, (ok, reason)): the Signature of aggregate_from_bytes and what verify(params, keys, messages,
+    that Signature) returns (BatchScheme.aggregate_verify_encoded: the challenges and hash_ag are computed once, not twice).
+    Raises ValueError as aggregate_from_bytes does."""
+    return _aggregate_from_bytes(params, keys, messages, blobs, True)
 
 
 def verify_signatures_from_bytes(params: Params, keys: List[OneTimeVerificationKey], messages: List[str],
@@ -772,13 +787,8 @@ def _groups_for_many(params: Params, keys_per_group, messages_per_group):
             [m for ms in messages_per_group for m in ms], [len(ks) for ks in keys_per_group])
 
 
-def aggregate_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],
-                              blobs_per_group: List[List[bytes]]) -> List[Signature]:
-    """NOT in the reference: aggregate_from_bytes for G committees at once -> [Signature] * G, entry g what
-    aggregate_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs_per_group[g]) returns
-    (BatchScheme.aggregate_many_encoded: one launch over all committees' bytes).  Raises ValueError, naming the group and the
-    record, for unequal numbers of groups, of keys, messages and blobs of a group, for a group without signers, for a blob of
-    the wrong length and for a record that is not canonical (the first one, with the reason)."""
+def _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, verify):
+    """aggregate_many_from_bytes (verify=False: no verdicts, None) and aggregate_verify_many_from_bytes: -> ([Signature] * G, verdicts)"""
     from fusion_hip import ENCODING_REASONS
     from fusion_hip.scheme import BatchScheme, encoded_size
     if len(blobs_per_group) != len(keys_per_group):
@@ -792,10 +802,11 @@ def aggregate_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeV
             if len(b) != size:
                 raise ValueError(f"group {g} record {i}: a 'signature' record is {size} bytes, not {len(b)}")
     if not sizes:
-        return []
+        return [], ([] if verify else None)
     bs = BatchScheme(params)
     try:
-        out, codes = bs.aggregate_many_encoded(vk_rows(), messages, b"".join(bytes(b) for blobs in blobs_per_group for b in blobs), sizes)
+        call = bs.aggregate_verify_many_encoded if verify else bs.aggregate_many_encoded
+        out, codes, *verdicts = call(vk_rows(), messages, b"".join(bytes(b) for blobs in blobs_per_group for b in blobs), sizes)
     finally:
         bs.close()
     bad = np.flatnonzero(codes)
@@ -803,7 +814,27 @@ def aggregate_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeV
         off = np.concatenate([[0], np.cumsum(sizes)])
         g = int(np.searchsorted(off, bad[0], side="right")) - 1
         raise ValueError(f"group {g} record {int(bad[0] - off[g])}: {ENCODING_REASONS[int(codes[bad[0]])]}")
-    return [Signature(signature_hat=_column(params, rows)) for rows in out]
+    return [Signature(signature_hat=_column(params, rows)) for rows in out], (verdicts[0] if verify else None)
+
+
+def aggregate_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],
+                              blobs_per_group: List[List[bytes]]) -> List[Signature]:
+    """NOT in the reference: aggregate_from_bytes for G committees at once -> [Signature] * G, entry g what
+    aggregate_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs_per_group[g]) returns
+    (BatchScheme.aggregate_many_encoded: one launch over all committees' bytes).  Raises ValueError, naming the group and the
+    record, for unequal numbers of groups, of keys, messages and blobs of a group, for a group without signers, for a blob of
+    the wrong length and for a record that is not canonical (the first one, with the reason)."""
+    return _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, False)[0]
+
+
+def aggregate_verify_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]],
+                                     messages_per_group: List[List[str]],
+                                     blobs_per_group: List[List[bytes]]) -> Tuple[List[Signature], List[Tuple[bool, str]]]:
+    """NOT in the reference: aggregate_verify_from_bytes for G committees at once -> ([Signature] * G, [(ok, reason)] * G), entry g
+    of each what aggregate_verify_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs_per_group[g]) returns
+    (BatchScheme.aggregate_verify_many_encoded: one launch for all committees' aggregates and verification targets, one for all
+    verdicts).  Raises ValueError as aggregate_many_from_bytes does."""
+    return _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, True)
 
 
 def verify_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],

@@ -119,6 +119,8 @@ SIGNATURES = {
     "fz_aggregate_encoded_async": (c_int, [_ctx, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_void_p, c_void_p]),
     "fz_aggregate_encoded_ragged_async": (c_int, [_ctx, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_size_t, c_int, c_int64,
                                                   c_void_p, c_size_t, c_void_p]),
+    "fz_aggregate_target_encoded_ragged_async": (c_int, [_ctx, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_size_t), c_size_t,
+                                                         c_int, c_int64, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "fz_verify_encoded_async": (c_int, [_ctx, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fz_target_partial": (c_int, [_ctx, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "fz_reduce_i64": (c_int, [_ctx, c_void_p, c_void_p, c_size_t]),

@@ -464,6 +464,18 @@ class Context:
             self._h, c_void_p(d_bytes or None), c_void_p(d_alpha or None), c_void_p(d_skip or None), off, len(offsets) - 1, l, bound,
             c_void_p(d_partial), partial_stride, c_void_p(d_out or None)))
 
+    def aggregate_target_encoded_ragged_async_dev(self, d_bytes, d_alpha, d_skip, d_vk, d_c_hat, offsets, l, bound, d_partial,
+                                                  partial_stride, d_target_partial, target_stride, d_out):
+        """aggregate_encoded_ragged_async_dev with every group's verification target in the same launch: d_partial and d_out as
+        that call leaves them; the int64 target partial [d] of group g at d_target_partial + g * target_stride is what
+        aggregate_target_partial_ragged_dev(0, ...) leaves for the group's signers with d_skip[i] == 0, from d_vk [N][2][d] and
+        d_c_hat [N][d] (asynchronous; the offsets are read before the call returns)"""
+        off = (ctypes.c_size_t * len(offsets))(*[int(x) for x in offsets])
+        check(self._lib, self._lib.fz_aggregate_target_encoded_ragged_async(
+            self._h, c_void_p(d_bytes or None), c_void_p(d_alpha or None), c_void_p(d_skip or None), c_void_p(d_vk or None),
+            c_void_p(d_c_hat or None), off, len(offsets) - 1, l, bound, c_void_p(d_partial), partial_stride,
+            c_void_p(d_target_partial), target_stride, c_void_p(d_out or None)))
+
     def verify_encoded_async_dev(self, d_A, d_bytes, N, l, bound, d_target, d_vk, d_c_hat, d_verdicts):
         """the verdicts (0, 3, 6) of N encoded records of l rows straight from their bytes, against d_target [N][d] or, with
         d_target 0 / None, against the targets formed from d_vk [N][2][d] and d_c_hat [N][d] (asynchronous)"""

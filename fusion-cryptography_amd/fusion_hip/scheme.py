@@ -735,7 +735,8 @@ class BatchScheme:
         signatures (2.46 times the bytes at secpar 256) never exist on the device.
         What this call does NOT do: a canonical record is within the norm bound of ONE signature, but its target equation
         A (.) sig_i == vkL_i (.) c_i + vkR_i is not checked.  An aggregator of mostly honest input verifies its own aggregate
-        (verify); when that fails, aggregate_encoded_screened on the same bytes names the signer.
+        (aggregate_verify_encoded does both in one pass; verify afterwards repeats the challenge pass and hash_ag); when that
+        fails, aggregate_encoded_screened on the same bytes names the signer.
         A length that is not N whole records, or numbers of keys / messages other than N, raise FusionHipError(FZ_E_BADARG)
         before the device is touched."""
         nrows, bound, rb, data, n = self._signature_records(vk, messages, data)
@@ -902,18 +903,11 @@ class BatchScheme:
         one download.  Sizes that do not sum to the numbers of records, keys and messages, a size below 1, or a length that is
         not whole records raise FusionHipError(FZ_E_BADARG) before the device is touched; no records and sizes == [] return
         empty arrays without a device."""
-        nrows, _, bound, _, rb = _encoding(self.params, "signature")
-        _, _, abound, _, arb = _encoding(self.params, "aggregate")
-        data, n = _records_input("signature", data, rb)
-        sizes = self._many_sizes(vk, messages, sizes)
-        self._check_dev(vk, (sum(sizes), 2, self.d))
-        if sum(sizes) != n:
-            raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {n} records were given")
+        nrows, bound, rb, data, n, sizes = self._signature_groups(vk, messages, data, sizes)
         g = len(sizes)
         if g == 0:
-            codes = np.zeros(0, dtype=np.int32)
-            return (np.zeros((0, arb), dtype=np.uint8), codes, np.zeros(0, dtype=np.int32)) if encoded else \
-                (np.zeros((0, self.l, self.d), dtype=np.int32), codes)
+            out, extras = self._aggregates_out(None, None, 0, encoded)
+            return (out, np.zeros(0, dtype=np.int32)) + extras
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         with DeviceScope() as s:
             dB = self._records_dev(s, data, n, rb)
@@ -932,11 +926,91 @@ class BatchScheme:
             dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, codes == 0)
             dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
             self.ctx.aggregate_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, off, self.l, bound, dP.ptr, self.l * self.d, dO.ptr)
-            if not encoded:
-                return dO.numpy(), codes
-            dR, dW = self._new(s, (g, arb), np.uint8), self._new(s, (g,))
-            self.ctx.encode_records_async_dev(dO.ptr, g, self.l, True, abound, dR.ptr, dW.ptr)
-            return dR.numpy(), codes, dW.numpy()
+            out, extras = self._aggregates_out(s, dO, g, encoded)
+            return (out, codes) + extras
+
+    def _signature_groups(self, vk, messages, data, sizes):
+        """the input of the calls that take groups of "signature" records, refused with FusionHipError(FZ_E_BADARG) unless it is
+        whole records and the sizes, each at least 1, sum to the numbers of records, keys and messages; no device is touched:
+        -> (nrows, bound, rb, data, n, sizes)"""
+        nrows, _, bound, _, rb = _encoding(self.params, "signature")
+        data, n = _records_input("signature", data, rb)
+        sizes = self._many_sizes(vk, messages, sizes)
+        self._check_dev(vk, (sum(sizes), 2, self.d))
+        if sum(sizes) != n:
+            raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {n} records were given")
+        return nrows, bound, rb, data, n, sizes
+
+    def _aggregates_out(self, s, dO, g, encoded):
+        """how the many-committee calls from the bytes hand back the g aggregates dO [g][l][d] holds on the device: -> (rows
+        [g][l][d] int32, ()), or with encoded (records uint8 [g][encoded_size(params, "aggregate")], (aggregate_codes int32 [g],))
+        -- the aggregates are then never downloaded as rows; g == 0: the empty arrays, no device"""
+        _, _, abound, _, arb = _encoding(self.params, "aggregate")
+        if g == 0:
+            return (np.zeros((0, arb), dtype=np.uint8), (np.zeros(0, dtype=np.int32),)) if encoded else \
+                (np.zeros((0, self.l, self.d), dtype=np.int32), ())
+        if not encoded:
+            return dO.numpy(), ()
+        dR, dW = self._new(s, (g, arb), np.uint8), self._new(s, (g,))
+        self.ctx.encode_records_async_dev(dO.ptr, g, self.l, True, abound, dR.ptr, dW.ptr)
+        return dR.numpy(), (dW.numpy(),)
+
+    # ---- aggregate and verify in one pass, straight from the bytes (not in the reference; INTEGRATION.md section G) ---------
+    def aggregate_verify_many_encoded(self, vk, messages, data, sizes, encoded=False):
+        """aggregate_many_encoded followed, per group, by verify() of the group's aggregate on its accepted signers, as an
+        aggregator that checks its own output does, in ONE pass: -> (aggregates [G][l][d] int32, codes int32 [sum N], verdicts),
+        or with encoded=True (records uint8 [G][encoded_size(params, "aggregate")], codes, aggregate_codes int32 [G], verdicts).
+        Rows, codes (0 or 6) and aggregate_codes are bit for bit aggregate_many_encoded's; verdicts[g] is bit for bit
+        verify(vk_g[ok], messages_g[ok], aggregate_g) over the group's records with code 0 -- (bool, reason), the capacity
+        refusal for more than params.capacity accepted signers included (no arithmetic decides it, and the aggregate is still
+        returned) -- and None where the group has no accepted signer (its row is zero).
+        One upload of the bytes, one range check whose status words stay on the device as the skip words, one upload of vk (the
+        challenge pass and the fused launch read the same copy), one challenge pass with c_hat kept on the device, hash_ag ONCE
+        per group -- the two calls in sequence run it, the key sort and the challenge pass twice --, one upload + transform of
+        the coefficients, ONE launch for all aggregates' and all targets' int64 sums
+        (fz_aggregate_target_encoded_ragged_async), one for all verdicts straight from the sums
+        (fz_verify_partials_batch_async), one download.  Refusals are aggregate_many_encoded's, raised before the device is
+        touched; no records and sizes == [] return empty arrays and [] without a device."""
+        nrows, bound, rb, data, n, sizes = self._signature_groups(vk, messages, data, sizes)
+        g = len(sizes)
+        if g == 0:
+            out, extras = self._aggregates_out(None, None, 0, encoded)
+            return (out, np.zeros(0, dtype=np.int32)) + extras + ([],)
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        with DeviceScope() as s:
+            dB = self._records_dev(s, data, n, rb)
+            dV = self._new(s, (n,))
+            self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
+            dK = self._take(s, vk, (n, 2, self.d))
+            dC, c_hat, pre = self._challenges_both(dK, messages, scope=s)      # beside the check
+            _, L, R = self._split_vk(vk)
+            codes = dV.numpy()
+            valid = codes == 0
+            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, valid)
+            dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
+            dT, dW = self._new(s, (g, self.d), np.int64), self._new(s, (g,))
+            self.ctx.aggregate_target_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, dK.ptr, dC.ptr, off, self.l, bound, dP.ptr,
+                                                               self.l * self.d, dT.ptr, self.d, dO.ptr)
+            self.ctx.verify_partials_batch_async_dev(self._A_dev().ptr, dP.ptr, self.l * self.d, dT.ptr, self.d, g, self.l,
+                                                     int(self.params.beta_vf), int(self.params.omega_vf), dW.ptr)
+            out, extras = self._aggregates_out(s, dO, g, encoded)
+            accepted = np.add.reduceat(valid.astype(np.int64), off[:-1])
+            verdicts = [None if a == 0 else (False, VERDICT_REASONS[1]) if a > self.params.capacity else _verdict(c)
+                        for a, c in zip(accepted, dW.numpy())]
+            return (out, codes) + extras + (verdicts,)
+
+    def aggregate_verify_encoded(self, vk, messages, data):
+        """aggregate_encoded followed by verify() of the result on the accepted signers, in one pass (the many-committee form
+        with one group): -> (aggregate [l][d] int32, codes int32 [N], (ok, reason)).  aggregate and codes are
+        aggregate_encoded's; the verdict is bit for bit verify(vk[ok], messages[ok], aggregate) over the records with code 0,
+        its capacity refusal included.  No canonical record (or N == 0): (None, codes, None).  hash_ag, the challenge pass and
+        the key sort run once where aggregate_encoded + verify run them twice.  A length that is not N whole records, or
+        numbers of keys / messages other than N, raise FusionHipError(FZ_E_BADARG) before the device is touched."""
+        n = _records_input("signature", data, _encoding(self.params, "signature")[4])[1]
+        aggs, codes, verdicts = self.aggregate_verify_many_encoded(vk, messages, data, [n] if n else [])
+        if not verdicts or verdicts[0] is None:
+            return None, codes, None
+        return aggs[0], codes, verdicts[0]
 
     def verify_many_encoded(self, vk, messages, data, sizes):
         """G independent verify_encoded calls as one batch: `data` holds G "aggregate" records (every form decode takes), vk and

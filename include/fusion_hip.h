@@ -435,6 +435,24 @@ FZ_API int fz_aggregate_encoded_ragged_async(fz_ctx *ctx, const uint8_t *d_bytes
                                              const size_t *h_offsets, size_t groups, int l, int64_t bound, int64_t *d_partial,
                                              size_t partial_stride, int32_t *d_out);
 
+/* the same with every group's verification target beside its aggregate, in the same launch ("Aggregate
+ * and verify in one pass"): what an aggregator that checks its own output hands to fz_verify_partials_batch_async.  d_partial and
+ * d_out hold, bit for bit, what fz_aggregate_encoded_ragged_async leaves for the same arguments.  Group g's int64 target partial
+ * [degree] lies at d_target_partial + g * target_stride and holds, bit for bit, what fz_aggregate_target_partial_ragged leaves
+ * with d_sig == NULL for group g's signers with d_skip[i] == 0: the sum of (vkL_i (.) c_i mod q + vkR_i) (.) alpha_hat_i mod q,
+ * from d_vk [N][2][degree] (vkL_i then vkR_i, as keygen writes it; read in place) and d_c_hat [N][degree], any int32 values.  A
+ * skipped signer contributes to neither sum, and neither its bytes nor its key are read.  The call clears exactly the partials it
+ * owns, of both kinds: the words between two partials are not touched; a group of zero signers, or one whose every signer is
+ * skipped, leaves zero partials of both kinds.  The rules of fz_aggregate_encoded_ragged_async in their order, then FZ_E_BADARG
+ * for a NULL d_target_partial, for a NULL d_vk or d_c_hat (unless every group is empty), for d_vk or d_c_hat not 16-byte aligned
+ * or d_target_partial not 8-byte aligned, and for target_stride < degree or an odd target_stride with groups > 1; groups == 0
+ * does nothing and writes nothing.  More than 64 groups run as several launches.  Asynchronous on the context's stream,
+ * allocation-free, capturable by fz_graph_* (the clears are part of the captured work; the offsets are those of the capture). */
+FZ_API int fz_aggregate_target_encoded_ragged_async(fz_ctx *ctx, const uint8_t *d_bytes, const int32_t *d_alpha_hat, const int *d_skip,
+                                                    const int32_t *d_vk, const int32_t *d_c_hat, const size_t *h_offsets, size_t groups,
+                                                    int l, int64_t bound, int64_t *d_partial, size_t partial_stride,
+                                                    int64_t *d_target_partial, size_t target_stride, int32_t *d_out);
+
 /* verdicts of N encoded records against their targets, straight from the bytes */
 /* Record i is l rows of w-bit fields u = z + bound, z = cent(INTT(row)), exactly what fz_encode_records_async writes for a
  * signature or an aggregate.  d_verdicts[i] = FZ_VERDICT_ENCODING (6) when some field of record i is above 2 * bound (the
