@@ -109,9 +109,9 @@ struct fz_ctx {
     uint32_t *d_mt_init;         // MT19937 state after init_genrand(19650218) (fz_sample_secret_polys_dev), lazily
     int chal_tab_ib, chal_tab_degree;   // what the table in FZ_A_CHAL_TAB was built for
     // Pinned, device-visible staging for the SMALL host inputs of the fused challenge kernel (message bytes + offsets, or the
-    // digests): the kernel reads them in place over the host link (three coalesced requests per wave), so a call uploads
-    // nothing and does not synchronise.  Two slots in turn; a slot's event is recorded after the launch that reads it and
-    // waited for before the slot is written again.
+    // digests) and of the sampler (the seeds): the kernel reads them in place over the host link (three coalesced requests per
+    // wave), so a call uploads nothing and does not synchronise.  Two slots in turn; a slot's event is recorded after the launch
+    // that reads it and waited for before the slot is written again (stage_take / stage_release, fz_staged_capi.hip).
     struct FzStage { uint8_t *h; size_t bytes; hipEvent_t ev; int busy; };
     FzStage chal_stage[2];
     int chal_stage_next;
@@ -382,7 +382,9 @@ int fz_launch_verify_fused(fz_ctx *ctx, const int32_t *A, const int32_t *sig, co
 int fz_launch_verify_signatures(fz_ctx *ctx, const int32_t *A, const int32_t *sig, const int32_t *vk, const int32_t *c, size_t N,
                                 int l, int64_t beta, int64_t omega, int *d_verdict);
 
-// challenge pipeline on the device (fz_challenge.hip) and the pieces it shares with the host serialiser (fz_host.cpp)
+// challenge pipeline on the device (fz_challenge.hip; its entries and their host side: fz_staged_capi.hip) and the pieces it shares
+// with the host serialiser (fz_host.cpp)
+constexpr int kFzShakeRate = 136;        // SHAKE-256 / SHA3-256 rate in bytes (17 lanes of 64 bits): a block of text, of stream
 struct fz_scheme_params;
 int fz_launch_challenge(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *d_pre, const uint32_t *d_dec, size_t N,
                         uint8_t *d_text, size_t text_stride, int *d_nblocks, uint32_t *d_xof, size_t xstride, int out_blocks,

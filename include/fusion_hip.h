@@ -563,7 +563,8 @@ FZ_API int fz_aggregation_coefficients(const fz_scheme_params *P, const int32_t 
  * once).  Only as many XOF bytes are squeezed as the decoder consumes (a prefix of the reference's n).  Supported: ternary
  * challenges (norm bound 1: both parameter sets of the reference), degree 4..256; otherwise FZ_E_UNSUPPORTED -- use
  * fz_challenge_coefficients.
- * hash_ag (fusion.py:632-652) stays on the host: it is ONE serial XOF over all signers by construction. */
+ * hash_ag (fusion.py:632-652) stays on the host: it is ONE serial XOF over all signers by construction.
+ * (The entries: csrc/fz_staged_capi.hip, with the device sampler's below; the kernels: csrc/fz_challenge.hip.) */
 FZ_API int fz_challenge_coefficients_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash,
                                          size_t N, int32_t *d_coefs);
 FZ_API int fz_challenge_hat_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash,

@@ -1,7 +1,8 @@
-"""Every entry of csrc/fz_capi.hip without a GPU: which refusal wins, which runtime calls it makes, where in which area every
-pointer it hands a launcher lies.
+"""Every entry of csrc/fz_capi.hip (the int32-row entries) and csrc/fz_staged_capi.hip (the challenge pipeline's and the sampler's, which
+take their small host inputs through the pinned staging slots) without a GPU: which refusal wins, which runtime calls it makes, where
+in which area every pointer it hands a launcher lies.
 
-fz_capi.hip, fz_context.hip and fz_diag.hip are compiled for the host with fz_host.cpp under AddressSanitizer and UBSan and linked,
+fz_capi.hip, fz_staged_capi.hip, fz_context.hip and fz_diag.hip are compiled for the host with fz_host.cpp under AddressSanitizer and UBSan and linked,
 as a stand-alone program, against the stub HIP runtime of tests/_hip_stub.py and recording stand-ins for every fz_launch_*.  A
 stand-in records the counts and every pointer it was handed: a pointer into a growable area of the context, a staging slot or
 the sampler's table as that area's name plus the byte offset, a caller's pointer as its argument's name plus the offset.  The
@@ -21,7 +22,7 @@ memory), three calls in a row (the two slots in turn, the wait on reuse), a long
 sampler in its two forms (N = 4096, 4097) with its refusals, the table uploaded on first use only.
 
 tests/golden/capi_entries.txt is that output for the sources BEFORE the entries' rules and scratch layouts were written once
-(docs/HISTORY.md section AA): the refactored unit must reproduce it line for line."""
+(docs/HISTORY.md section AA), all of them still in fz_capi.hip: the refactored units must reproduce it line for line."""
 import os
 import re
 import subprocess
@@ -30,7 +31,7 @@ import pytest
 
 from _hip_stub import CSRC, STUB, build_driver
 
-UNITS = ("fz_capi", "fz_context", "fz_diag")
+UNITS = ("fz_capi", "fz_staged_capi", "fz_context", "fz_diag")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "capi_entries.txt")
 
 DRIVER_BODY = r'''
@@ -582,13 +583,15 @@ def parsed(lines):
 
 
 def test_every_entry_of_the_unit_is_walked(lines):
-    """every extern "C" function of fz_capi.hip has its lines on every context it is walked on, with the good call and the empty one"""
-    text = open(os.path.join(CSRC, "fz_capi.hip")).read()
-    exported = set(re.findall(r"^int (fz_\w+)\(", text, re.M))
-    assert len(exported) >= 40
+    """every extern "C" function of the two units has its lines on every context it is walked on, with the good call and the empty
+    one; the entries with walks of their own (challenge_walk, sampler_walk) are exactly those of fz_staged_capi.hip"""
+    rows, staged = (set(re.findall(r"^int (fz_\w+)\(", open(os.path.join(CSRC, unit + ".hip")).read(), re.M)) for unit in ("fz_capi", "fz_staged_capi"))
+    exported = rows | staged
+    assert len(exported) >= 40 and not rows & staged
     table = parsed(lines)
     assert {e for _, e in table} == exported
     special = ("fz_challenge_coefficients_dev", "fz_challenge_hat_dev", "fz_challenge_hat_msgs_dev", "fz_sample_secret_polys_dev")
+    assert staged == set(special)
     for e in exported - set(special):
         for c in ("d256", "d64", "d128", "ring12", "q32"):
             assert {"good", "empty"} <= set(table[(c, e)]), (c, e)

@@ -94,7 +94,7 @@ def test_fixtures_reach_every_edge(name):
     assert len({len(str(fx.ints[k])) for k in sw}) >= 2
     if ps.scheme or name == "d128w64":                       # keys that differ only in how many values have two digits
         assert all(set(np.unique(fx.vk[k])) <= {7, 12} for k in sw)
-    # the longest text fits the row that challenge_dev (csrc/fz_capi.hip) sizes: 13 bytes per value and 78 digits
+    # the longest text fits the row that challenge_geometry (csrc/fz_staged_capi.hip) sizes: 13 bytes per value and 78 digits
     s0, s1, s2 = E.text_pieces(ps)
     blocks = (len(s0) + len(s1) + len(s2) + 2 * ps.degree * 13 + 78) // E.RATE + 1
     blocks += blocks & 1

@@ -235,15 +235,6 @@ int fz_launch_verify_fused_i64(fz_ctx *, const int32_t *, const int64_t *, size_
 int fz_launch_verify_signatures(fz_ctx *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, size_t N, int l, int64_t, int64_t, int *) { return recd("verify_signatures", {U(N), U(l)}); }
 int fz_launch_polymul_fused(fz_ctx *, const int32_t *, const int32_t *, int32_t *, size_t batch) { return recd("polymul_fused", {U(batch)}); }
 bool fz_polymul16_ok(const fz_ctx *, const int32_t *, const int32_t *, const int32_t *, size_t) { return false; }
-int fz_launch_prehash(fz_ctx *, const fz_scheme_params *, const uint8_t *, const unsigned long long *, size_t, uint8_t *, uint32_t *) { return FZ_OK; }
-int fz_launch_challenge(fz_ctx *, const fz_scheme_params *, const int32_t *, const uint8_t *, const uint32_t *, size_t, uint8_t *, size_t, int *, uint32_t *,
-                        size_t, int, const uint32_t *, int32_t *) { return FZ_OK; }
-int fz_launch_challenge_wave(fz_ctx *, const fz_scheme_params *, const int32_t *, const uint8_t *, const uint8_t *, const unsigned long long *, uint8_t *, size_t,
-                             size_t, int, const uint32_t *, int32_t *) { return FZ_OK; }
-int fz_launch_mt_sample(fz_ctx *, const unsigned long long *, size_t, int, uint32_t, int, const uint32_t *, int32_t *, int *, uint32_t *) { return FZ_OK; }
-void fz_mt_init_table(uint32_t *) {}
-bool fz_challenge_wave_ok(const fz_scheme_params *) { return false; }
-void fz_challenge_weight_table(int, int, uint32_t *) {}
 // the setup of each unit that is not linked
 int fz_records_query_grid(fz_ctx *) { return FZ_OK; }
 int fz_aggregate_encoded_query_grid(fz_ctx *) { return FZ_OK; }
