@@ -3,27 +3,14 @@
 #ifndef FZ_CHALLENGE_TEXT_DEV_H
 #define FZ_CHALLENGE_TEXT_DEV_H
 
-namespace {
+#include "fz_wave_text_dev.h"         // wave_sync, dec_len: shared with fz_hash_ag.hip
 
-// what one lane wrote to LDS before, every lane of the WAVE reads after (the waves of a workgroup never synchronise with each other)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+namespace {
 
 struct VkTextParts {                         // the fixed pieces of the text, built on the host once per call
     char s0[384], s1[384], s2[16];           // before the left values / between left and right / after the right values
     int n0, n1, n2;
 };
-
-__device__ __forceinline__ int dec_len(int v) {          // len(str(v)) for an int32
-    unsigned u = v < 0 ? 0u - (unsigned)v : (unsigned)v;
-    int n = (v < 0) ? 2 : 1;
-    n += u >= 10u; n += u >= 100u; n += u >= 1000u; n += u >= 10000u; n += u >= 100000u; n += u >= 1000000u;
-    n += u >= 10000000u; n += u >= 100000000u; n += u >= 1000000000u;
-    return n;
-}
 
 // str(int) of a 256-bit integer (eight 32-bit limbs, least significant first) in base 10^9: chunks out[0..n-1], least
 // significant first; returns n (1..9).  Nine rounds of an eight-limb short division: a sequential chain, one LANE's work.

@@ -316,6 +316,7 @@ static int ctx_create(int device_id, uint32_t q, int degree, uint32_t root, uint
         c->knob_matvec_slices = knob("FZ_MATVEC_SLICES");
         c->knob_verify_cent = knob("FZ_VERIFY_CENT");
         c->knob_multi_order = getenv("FZ_MULTI_ORDER") ? knob("FZ_MULTI_ORDER") : 1;
+        c->knob_hash_ag_order = getenv("FZ_HASH_AG_ORDER") ? knob("FZ_HASH_AG_ORDER") : 1;
         // fz_malloc's block pool: FZ_POOL_MB megabytes at most over all contexts of the process (default 4096, 0 = every fz_free is a hipFree)
         c->pool_cap = (size_t)(getenv("FZ_POOL_MB") ? (knob("FZ_POOL_MB") < 0 ? 0 : knob("FZ_POOL_MB")) : 4096) << 20;
     }

@@ -336,6 +336,18 @@ void put_vk(std::string &s, const fz_scheme_params &P, const int32_t *left, cons
     s += ")";
 }
 
+// one item of hash_ag's list (fusion.py:632-652): "(vk, int, SignatureChallenge(c_hat=poly))"
+void put_agg_item(std::string &s, const fz_scheme_params &P, const int32_t *left, const int32_t *right, const uint8_t prehash[32],
+                  const int32_t *c_hat) {
+    s += "(";
+    put_vk(s, P, left, right);
+    s += ", ";
+    s += u256_decimal(prehash);
+    s += ", SignatureChallenge(c_hat=";
+    put_poly(s, P, c_hat);
+    s += "))";
+}
+
 // ---- byte decoder -------------------------------------------------------------------------------------
 inline uint64_t be_mod(const uint8_t *p, int n, uint64_t m) {       // int.from_bytes(p[:n], "big") % m, m < 2^32
     if (m == 1) return 0;
@@ -536,6 +548,43 @@ size_t fz_host_challenge_needed_bytes(const fz_scheme_params *P, int *sign_bytes
 
 bool fz_host_params_ok(const fz_scheme_params *P) { return params_ok(P); }
 
+// ---- what the device hash_ag (fz_hash_ag.hip) shares with this file ---------------------------------------------------
+// The fixed pieces of one item of hash_ag's list around its three lists of values and the pre-hashed integer, cut out of
+// put_agg_item's own output for an all-zero item (so both pipelines have ONE definition of the text): q0 before the left
+// key values, q1 between the key's lists, q2a from the right values to the integer, q2b from the integer to the challenge's
+// values, q3 after them.  n[0..4] their lengths, n[0] = -1 if a piece does not fit (cap for q0, q1, q2b; 16 for q2a, q3).
+void fz_host_agg_text_parts(const fz_scheme_params *P, char *q0, char *q1, char *q2a, char *q2b, char *q3, int *n, int cap) {
+    const int d = P->degree;
+    std::vector<int32_t> zeros((size_t)d, 0);
+    const uint8_t zero_pre[32] = {0};
+    std::string t;
+    put_agg_item(t, *P, zeros.data(), zeros.data(), zero_pre, zeros.data());
+    const size_t zl = (size_t)3 * d - 2;                              // "0, 0, ..., 0"
+    const size_t a = t.find("values=[") + 8;
+    const size_t b = t.find("values=[", a) + 8;
+    const size_t c = t.find("values=[", b) + 8;
+    const size_t k = t.find(", 0, ", b + zl) + 2;                     // the integer "0" sits at k
+    const std::string p0 = t.substr(0, a), p1 = t.substr(a + zl, b - (a + zl)), p2a = t.substr(b + zl, k - (b + zl)),
+                      p2b = t.substr(k + 1, c - (k + 1)), p3 = t.substr(c + zl);
+    n[0] = -1;
+    if ((int)p0.size() > cap || (int)p1.size() > cap || (int)p2b.size() > cap || p2a.size() > 16 || p3.size() > 16) return;
+    memcpy(q0, p0.data(), p0.size());
+    memcpy(q1, p1.data(), p1.size());
+    memcpy(q2a, p2a.data(), p2a.size());
+    memcpy(q2b, p2b.data(), p2b.size());
+    memcpy(q3, p3.data(), p3.size());
+    n[0] = (int)p0.size(); n[1] = (int)p1.size(); n[2] = (int)p2a.size(); n[3] = (int)p2b.size(); n[4] = (int)p3.size();
+}
+
+// the decoder's shape for hash_ag's sections (fusion.py:579-585, :422-481): -> agg_coef_bytes, the bytes of ONE signer's section
+size_t fz_host_agg_section_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes) {
+    const DecodeShape s = decode_shape(P->secpar, P->modulus, P->degree, P->beta_ag, P->omega_ag);
+    if (sign_bytes) *sign_bytes = s.sign_bytes;
+    if (coef_bytes) *coef_bytes = s.coef_bytes;
+    if (index_bytes) *index_bytes = s.index_bytes;
+    return agg_coef_bytes(*P);
+}
+
 extern "C" {
 
 const char *fz_keccak_variant(void) { return g_keccak_name; }
@@ -613,9 +662,9 @@ int fz_challenge_coefficients(const fz_scheme_params *P, const int32_t *h_vk_lef
     return bad ? fz_set_error(FZ_E_BADARG, "Too few bytes to decode polynomial") : FZ_OK;
 }
 
-int fz_sort_by_vk_string(const fz_scheme_params *P, const int32_t *h_vk_left, const int32_t *h_vk_right, size_t N,
-                         size_t *h_order, int threads) {
-    if (!params_ok(P) || !h_order || (N && (!h_vk_left || !h_vk_right))) return fz_set_error(FZ_E_BADARG, "bad argument");
+// the sort of fz_sort_by_vk_string and of every group of fz_sort_by_vk_string_ragged: h_order [N] = the rows 0 .. N-1 of the two arrays
+static void sort_rows_by_vk_string(const fz_scheme_params *P, const int32_t *h_vk_left, const int32_t *h_vk_right, size_t N, size_t *h_order,
+                                   int threads) {
     const int d = P->degree;
     // Every str(vk) starts with the same text up to the left polynomial's "values=[": the order is decided by what follows,
     // "v0, v1, ..".  The first K values (with their separators: an exact prefix of that text while K < degree) decide it for
@@ -637,6 +686,28 @@ int fz_sort_by_vk_string(const fz_scheme_params *P, const int32_t *h_vk_left, co
         const int c = keys[a].compare(keys[b]);
         return c ? c < 0 : full_of(a) < full_of(b);
     });
+}
+
+int fz_sort_by_vk_string(const fz_scheme_params *P, const int32_t *h_vk_left, const int32_t *h_vk_right, size_t N,
+                         size_t *h_order, int threads) {
+    if (!params_ok(P) || !h_order || (N && (!h_vk_left || !h_vk_right))) return fz_set_error(FZ_E_BADARG, "bad argument");
+    sort_rows_by_vk_string(P, h_vk_left, h_vk_right, N, h_order, threads);
+    return FZ_OK;
+}
+
+int fz_sort_by_vk_string_ragged(const fz_scheme_params *P, const int32_t *h_vk_left, const int32_t *h_vk_right, const size_t *h_off,
+                                size_t G, size_t *h_order, int threads) {
+    if (!params_ok(P) || (G && !h_off)) return fz_set_error(FZ_E_BADARG, "bad argument");
+    for (size_t g = 0; g < G; ++g)
+        if (h_off[g] > h_off[g + 1]) return fz_set_error(FZ_E_BADARG, "offsets must not decrease");
+    if (G && h_off[G] > h_off[0] && (!h_vk_left || !h_vk_right || !h_order)) return fz_set_error(FZ_E_BADARG, "bad argument");
+    const size_t d = (size_t)P->degree;
+    // independent groups: one sort each, spread over the host threads (a group of 16 keys is a few microseconds)
+    parallel_for(G, G >= 64 ? threads : 1, [&](size_t g) {
+        const size_t a = h_off[g], n = h_off[g + 1] - a;
+        sort_rows_by_vk_string(P, h_vk_left + a * d, h_vk_right + a * d, n, h_order + a, 1);
+        for (size_t i = 0; i < n; ++i) h_order[a + i] += a;
+    });
     return FZ_OK;
 }
 
@@ -654,15 +725,8 @@ int fz_aggregation_coefficients(const fz_scheme_params *P, const int32_t *h_vk_l
     // ahead unthrottled -- 14 MB of text at most -- so they are done early, and with one thread everything stays sequential.)
     std::vector<std::string> items(N);
     auto write_item = [&](size_t i) {
-        std::string &s = items[i];
-        s.reserve(16384);
-        s += "(";
-        put_vk(s, *P, h_vk_left + i * (size_t)d, h_vk_right + i * (size_t)d);
-        s += ", ";
-        s += u256_decimal(h_prehash + 32 * i);
-        s += ", SignatureChallenge(c_hat=";
-        put_poly(s, *P, h_c_hat + i * (size_t)d);
-        s += "))";
+        items[i].reserve(16384);
+        put_agg_item(items[i], *P, h_vk_left + i * (size_t)d, h_vk_right + i * (size_t)d, h_prehash + 32 * i, h_c_hat + i * (size_t)d);
     };
     std::unique_ptr<std::atomic<unsigned char>[]> ready(new std::atomic<unsigned char>[N ? N : 1]);
     for (size_t i = 0; i < N; ++i) ready[i].store(0, std::memory_order_relaxed);

@@ -126,6 +126,7 @@ struct fz_ctx {
     int knob_matvec_slices;      // FZ_MATVEC_SLICES = 1 | 2 | 4: k-range slices per column of the integer matvec kernel (0 = by batch size, -1 = the fp64 kernel)
     int knob_no_imad;            // FZ_NO_IMAD=1: A (.) y through the general fp64 multiply instead of integer multiply-adds (A/B runs)
     int knob_verify_cent;        // FZ_VERIFY_CENT=1: centre the inverse transform's outputs before the norm test even when beta allows skipping it
+    int knob_hash_ag_order;      // FZ_HASH_AG_ORDER=0: the device hash_ag hands its waves the committees in the caller's order (1, the default: longest first)
     int knob_multi_order;        // FZ_MULTI_ORDER=0: a multi-job launch runs its jobs in table order, streaming stores throughout (1, the default: fz_multi_plan)
     // the previous multi-job launch's outputs in the order they were produced (host memory, written when a launch is issued or
     // CAPTURED: a graph replays the order it was captured with)
@@ -403,6 +404,16 @@ void fz_challenge_weight_table(int index_bytes, int degree, uint32_t *h_tab);   
 void fz_host_vk_text_parts(const fz_scheme_params *P, char *s0, int *n0, char *s1, int *n1, char *s2, int *n2, int cap);
 size_t fz_host_challenge_needed_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes);
 bool fz_host_params_ok(const fz_scheme_params *P);
+
+// hash_ag for many committees on the device (fz_hash_ag.hip; its entry: fz_hash_ag_capi.hip) and the pieces it shares with the host
+// serialiser (fz_host.cpp)
+bool fz_hash_ag_wave_ok(const fz_scheme_params *P, const char **why);   // *why (optional): the message of the refusal
+// ord [M] row indices and grp [G] pairs of uint32 (first entry of ord, signers >= 1), both device-visible; one coefficient row of
+// d_alpha per entry of ord, nothing else written
+int fz_launch_hash_ag(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *d_pre, const int32_t *d_c_hat,
+                      const uint32_t *ord, const void *grp, size_t G, const uint32_t *d_tab, int32_t *d_alpha);
+void fz_host_agg_text_parts(const fz_scheme_params *P, char *q0, char *q1, char *q2a, char *q2b, char *q3, int *n, int cap);
+size_t fz_host_agg_section_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes);
 
 // launchers of the streaming kernels (fz_pointwise.hip; fz_launch_aggregate: fz_aggregate.hip)
 int fz_launch_fill_synthetic(fz_ctx *ctx, int32_t *out, size_t count, unsigned long long seed);

@@ -2,35 +2,11 @@
 // and therefore refuse graph capture: the host side of the device challenge pipeline (fz_challenge.hip) and of the device sampler
 // (fz_sample.hip).  No kernel.
 #include "fz_capi_rules.h"
+#include "fz_staged_rules.h"      // the pinned staging slots' protocol and the decoder's cached weight table
 
 #include <cstring>
 #include <algorithm>
 #include <vector>
-
-// ---- the pinned staging slots (fz_internal.h), shared by the challenge pipeline's wave form and the sampler ---------------------
-// The protocol: stage_take, fill the slot, the launches that read it, stage_release with what they returned.
-// stage_take: the next slot, at least `bytes` long and no longer read by any launch
-static int stage_take(fz_ctx *ctx, size_t bytes, fz_ctx::FzStage **out) {
-    fz_ctx::FzStage &st = ctx->chal_stage[ctx->chal_stage_next];
-    ctx->chal_stage_next ^= 1;
-    if (!st.ev) FZ_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), "staging event");
-    if (st.busy) { FZ_HIP(hipEventSynchronize(st.ev), "staging slot still in use"); st.busy = 0; }
-    if (st.bytes < bytes) {
-        if (st.h) { FZ_HIP(hipHostFree(st.h), "staging free"); st.h = nullptr; st.bytes = 0; }
-        const size_t want = std::max<size_t>((bytes + 65535) & ~(size_t)65535, 256 << 10);
-        FZ_HIP(hipHostMalloc((void **)&st.h, want, hipHostMallocDefault), "staging alloc");
-        st.bytes = want;
-    }
-    *out = &st;
-    return FZ_OK;
-}
-// stage_release: the slot's event is recorded and the slot marked in use BEFORE the launches' code `rc` is looked at (a sequence that
-// failed half-way may have queued a reader); -> rc, or the record's own error
-static int stage_release(fz_ctx *ctx, fz_ctx::FzStage *st, int rc) {
-    FZ_HIP(hipEventRecord(st->ev, ctx->stream), "staging event record");
-    st->busy = 1;
-    return rc;
-}
 
 // ---- the challenge pipeline on the device (device half) ---------------------------------------------
 // the pre-hashed messages come either as h_prehash [N][32] (computed by the caller, fz_hash_messages) or are computed here,
@@ -82,22 +58,7 @@ static int challenge_geometry(ChalCall &c) {
     return FZ_OK;
 }
 
-// the decoder's weight table, cached in FZ_A_CHAL_TAB for the (index bytes, degree) it was built for
-static int challenge_table(ChalCall &c) {
-    fz_ctx *ctx = c.ctx;
-    const int ib = c.index_bytes, degree = c.P->degree;
-    if (!ctx->area[FZ_A_CHAL_TAB].p || ctx->chal_tab_ib != ib || ctx->chal_tab_degree != degree) {
-        std::vector<uint32_t> tab((size_t)(degree + 1) * 16);
-        fz_challenge_weight_table(ib, degree, tab.data());
-        ctx->chal_tab_degree = 0;                            // (no table is built for degree 0: a failure below leaves none that counts)
-        FZ_TRY(fz_area_replace(ctx, FZ_A_CHAL_TAB, tab.size() * 4));
-        FZ_HIP(hipMemcpy(ctx->area[FZ_A_CHAL_TAB].p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice), "table upload");
-        ctx->chal_tab_ib = ib;
-        ctx->chal_tab_degree = degree;
-    }
-    c.d_tab = (const uint32_t *)ctx->area[FZ_A_CHAL_TAB].p;
-    return FZ_OK;
-}
+static int challenge_table(ChalCall &c) { return challenge_table_fit(c.ctx, c.index_bytes, c.P->degree, &c.d_tab); }
 
 // One launch, nothing uploaded: the kernel reads the messages (or digests) from pinned host memory and leaves the
 // digests there.  The call returns without synchronising unless the caller wants the digests.

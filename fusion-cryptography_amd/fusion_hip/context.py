@@ -288,6 +288,21 @@ class Context:
             pre.ctypes.data_as(u8p) if want_prehash else ctypes.cast(None, u8p)))
         return pre
 
+    def hash_ag_ragged_dev(self, P, d_vk, d_pre, d_c_hat, N, order, offsets, d_alpha_hat):
+        """hash_ag with its transforms for len(offsets) - 1 independent committees in one launch, a wave per committee
+        (fz_hash_ag_ragged_dev): d_vk [N][2][d], d_pre [N][32] digests, d_c_hat [N][d] device pointers in the callers' row order;
+        order: row indices, offsets [G + 1] into it -- committee g hashes rows order[offsets[g]:offsets[g + 1]] in that order
+        (sorted by str(vk) by the caller).  d_alpha_hat [N][d]: row order[i] receives its coefficients' transform, every other
+        row zero.  Asynchronous; order and offsets are consumed when the call returns."""
+        order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+        off = np.ascontiguousarray(offsets, dtype=np.uintp).reshape(-1)
+        if off.shape[0] < 1 or int(off[-1]) != order.shape[0]:
+            raise FusionHipError(FZ_E_BADARG, f"{order.shape[0]} order entries, offsets end at {int(off[-1]) if off.shape[0] else None}")
+        check(self._lib, self._lib.fz_hash_ag_ragged_dev(
+            self._h, byref(P), c_void_p(d_vk or None), c_void_p(d_pre or None), c_void_p(d_c_hat or None), N,
+            order.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), off.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+            off.shape[0] - 1, c_void_p(d_alpha_hat or None)))
+
     def pw_dev(self, op, d_a, d_b, d_out, count):
         fn = {OP_MUL: self._lib.fz_pw_mul, OP_ADD: self._lib.fz_pw_add, OP_SUB: self._lib.fz_pw_sub}[op]
         check(self._lib, fn(self._h, c_void_p(d_a), c_void_p(d_b), c_void_p(d_out), count))

@@ -132,6 +132,21 @@ def sort_by_vk_string(P: SchemeParams, vk_left, vk_right, threads=None):
     return order.astype(np.int64)
 
 
+def sort_by_vk_string_ragged(P: SchemeParams, vk_left, vk_right, offsets, threads=None):
+    """sort_by_vk_string for every group of rows offsets[g]:offsets[g + 1] in one call: -> row indices into the whole arrays,
+    group after group, each group in the order sort_by_vk_string gives it alone (offsets from 0 to the number of rows)"""
+    lib = load_library()
+    d = P.degree
+    L, R = _rows(vk_left, d), _rows(vk_right, d)
+    off = np.ascontiguousarray(offsets, dtype=np.uintp).reshape(-1)
+    if off.shape[0] < 1 or int(off[0]) != 0 or int(off[-1]) != L.shape[0]:
+        raise ValueError(f"offsets must run from 0 to the {L.shape[0]} rows")
+    order = np.empty(L.shape[0], dtype=np.uintp)
+    check(lib, lib.fz_sort_by_vk_string_ragged(byref(P), _p(L), _p(R), off.ctypes.data_as(_SZP), off.shape[0] - 1,
+                                               order.ctypes.data_as(_SZP), threads or default_threads()))
+    return order.astype(np.int64)
+
+
 def aggregation_coefficients(P: SchemeParams, vk_left, vk_right, prehash, c_hat, threads=None):
     """inputs in sorted key order -> alpha coefficient rows [N][d]"""
     lib = load_library()

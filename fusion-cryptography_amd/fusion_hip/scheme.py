@@ -107,15 +107,43 @@ def screened_alpha_coefficients(P, L, R, pre, c_hat, valid=None, threads=None, o
     return order, alpha
 
 
+# ---- where the many-committee calls hash their aggregation coefficients (BatchScheme(hash_ag=...)) -------------------------
+# "auto" predicts both forms from the committees' sizes.  A signer costs _HASH_AG_PERMS permutations either way (its ~10 KB of
+# text absorbed, its section squeezed).  The device form is as long as its LONGEST committee's chain -- a wave's permutation takes
+# _HASH_AG_DEVICE_US alone on its SIMD and _HASH_AG_SHARED more per further wave there (1024 SIMDs, up to four waves each: 4096
+# committees in flight, then a second round) -- behind the ragged key sort, the upload of the pre-hashes and the launches.  The
+# host form is the summed work over the scheme's threads at _HASH_AG_HOST_US per permutation and thread, behind what every
+# committee costs the calling thread in Python.  All constants are medians of profiles/r25_hash_ag_many.txt (MI355X, 16
+# threads), which also shows the rule picking the faster form in every cell it measures.
+_HASH_AG_FORMS = ("host", "device", "auto")
+_HASH_AG_PERMS = {128: 30, 256: 99}           # per signer: (item text + section) / 136 (tools/probes/hash_ag_many.py)
+_HASH_AG_SIMDS, _HASH_AG_WAVES = 1024, 4      # 256 CUs x 4 SIMDs; the kernel's waves per SIMD (127 registers, 26 KB LDS per workgroup)
+_HASH_AG_DEVICE_US = 2.65                     # profiles/r25_hash_ag_many.txt: 64 x 64 at secpar 256, 16.81 ms / (64 x 99.2)
+_HASH_AG_SHARED = 0.37                        # ... 4096 x 64: 35.7 ms, 2.1 times the lone wave's at four waves per SIMD
+_HASH_AG_HOST_US = 0.2                        # ... 4096 x 64 against 4096 x 4 on the host: 0.15 (secpar 256) to 0.24 (128) per thread
+_HASH_AG_HOST_COMMITTEE_US = 110.0            # ... 4096 x 4: 0.104 ms of the calling thread per committee (64 x 4: 0.10 to 0.15)
+_HASH_AG_DEVICE_CALL_US = (500.0, 0.02)       # ... device - entry: 0.5 ms per call and 0.02 us per signer (sort, upload)
+
+
 class BatchScheme:
-    def __init__(self, params, device=0, threads=None, private_context=False):
+    hash_ag = "host"                     # (the defaults of an object made without __init__)
+    device_hash_ag = True
+
+    def __init__(self, params, device=0, threads=None, private_context=False, hash_ag="host"):
         """params: a fusion.fusion.Params (or any object with the same attributes).
+        hash_ag: where the many-committee calls (aggregate_many, verify_many and their _encoded forms) hash the committees'
+        aggregation coefficients: "host" (the default: one host thread per committee), "device" (one wave per committee,
+        fz_hash_ag_ragged_dev: c_hat is not downloaded and the coefficients are not uploaded) or "auto" (the device form where
+        it covers the parameter set and is predicted faster for the call's committee sizes).  The results are the same bit for
+        bit; a parameter set the device form does not cover falls back to the host once and stays there.
         private_context: give this object a context and a HIP stream of its own instead of the process-wide one per device.
         A context serves one host thread at a time (include/fusion_hip.h), so several BatchSchemes that are to work
         CONCURRENTLY -- one per worker thread -- each need their own.  That is how batches of the BASELINE size keep the chip
         busy: a 1024-signature sign_batch is a latency chain (108 Keccak permutations per signer on 32 waves: 0.63 of its
         0.87 ms) that leaves the other 250 CUs idle, and calls on separate streams overlap (tools/probes/concurrent_batches.py).
         close() releases the private context."""
+        if hash_ag not in _HASH_AG_FORMS:
+            raise FusionHipError(FZ_E_BADARG, f"hash_ag={hash_ag!r}: one of {_HASH_AG_FORMS}")
         self.params = params
         self.P = hostpipe.scheme_params(params)
         self.threads = threads or hostpipe.default_threads()
@@ -128,6 +156,8 @@ class BatchScheme:
             self.ctx.set_stream(self._stream)
         else:
             self.ctx = get_context(params.modulus, params.degree, params.root, params.inv_root, device)
+        self.hash_ag = hash_ag           # where the many-committee calls hash their coefficients (_hash_ag_form)
+        self.device_hash_ag = True       # ... its device form covers the parameter set (off after its first FZ_E_UNSUPPORTED)
         self.device_hash = True          # per-signer challenge pipeline on the device (falls back to the host if unsupported)
         self.device_sampler = True       # secret polynomials sampled on the device (the same fallback)
         self.A = np.array([z.values for row in params.public_challenge.matrix for z in row], dtype=np.int32)
@@ -462,21 +492,22 @@ class BatchScheme:
     def _signer_count(self, vk):
         return vk.shape[0] if isinstance(vk, DeviceArray) else np.asarray(vk).reshape(-1, 2, self.d).shape[0]
 
-    def _challenges_both(self, vk, messages, want_host=True, scope=None, want_dev=True):
+    def _challenges_both(self, vk, messages, want_host=True, scope=None, want_dev=True, want_pre=None):
         """hash_ch for every (key, message) in the CALLERS' order: -> (dC DeviceArray [N][d], c_hat host copy, prehash
         [N][32]).  THE place of the rule "the device pipeline where it covers the parameter set, else the C host pipeline"
         (FZ_E_UNSUPPORTED from the device once, and self.device_hash stays off).  The device pipeline leaves c_hat where the
         kernels need it; hash_ag needs a host copy of it as text input (want_host=False, no hash_ag behind the call: the
         device pipeline downloads neither, None for both).  want_dev=False (challenges()): nothing stays on the device, None
-        for dC, and the host pipeline uploads nothing.  dC is the caller's to free (dist.HipSteps), or with `scope` that
-        DeviceScope's."""
+        for dC, and the host pipeline uploads nothing.  want_pre (default: want_host): the prehashes without the host copy of
+        c_hat, for the device form of hash_ag.  dC is the caller's to free (dist.HipSteps), or with `scope` that DeviceScope's."""
+        want_pre = want_host if want_pre is None else want_pre
         if scope is None:
             with DeviceScope() as tmp:
-                dC, c_hat, pre = self._challenges_both(vk, messages, want_host, tmp, want_dev)
+                dC, c_hat, pre = self._challenges_both(vk, messages, want_host, tmp, want_dev, want_pre)
                 return (tmp.release(dC) if want_dev else None), c_hat, pre
         if self.device_hash:
             try:
-                dC, pre = self.challenges_dev(vk, messages, want_host, scope)
+                dC, pre = self.challenges_dev(vk, messages, want_pre, scope)
                 return (dC if want_dev else None), (dC.numpy() if want_host else None), pre
             except FusionHipError as e:
                 if e.code != FZ_E_UNSUPPORTED:
@@ -827,12 +858,91 @@ class BatchScheme:
             raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {nk} keys and {len(messages)} messages were given")
         return sizes
 
-    def _alpha_hat_many(self, scope, off, L, R, pre, c_hat, valid=None):
+    def _hash_ag_form(self, sizes):
+        """"host" or "device": where a many-committee call over committees of `sizes` hashes its coefficients (self.hash_ag; the
+        rule of "auto" and its constants: _HASH_AG_* above)"""
+        if self.hash_ag == "host" or not self.device_hash_ag or not len(sizes):
+            return "host"
+        if self.hash_ag == "device":
+            return "device"
+        perms = _HASH_AG_PERMS.get(getattr(self.params, "secpar", None), 99)
+        g, n = len(sizes), sum(sizes)
+        resident = _HASH_AG_SIMDS * _HASH_AG_WAVES
+        sharing = min(_HASH_AG_WAVES, -(-g // _HASH_AG_SIMDS)) - 1
+        chain = max(sizes) * perms * _HASH_AG_DEVICE_US * (1 + _HASH_AG_SHARED * sharing)
+        device = _HASH_AG_DEVICE_CALL_US[0] + _HASH_AG_DEVICE_CALL_US[1] * n + -(-g // resident) * chain
+        host = g * _HASH_AG_HOST_COMMITTEE_US + n * perms * _HASH_AG_HOST_US / max(1, min(self.threads, g))
+        return "device" if device < host else "host"
+
+    def _many_inputs(self, scope, vk, messages, sizes, want_dev=True):
+        """the challenge pass of a many-committee call in the form its hash_ag takes (_hash_ag_form): -> (dK, dC, c_hat, pre).
+        Device form: vk on the device (dK, an upload into `scope` unless it is there; the challenge pass reads the same copy),
+        c_hat stays there (None for the host copy), the prehashes come back.  Host form: dK None (nothing the call did not
+        upload before), the host copies of c_hat and the prehashes, and dC unless want_dev is False."""
+        if self._hash_ag_form(sizes) == "device":
+            dK = self._take(scope, vk, (int(sum(sizes)), 2, self.d))
+            dC, c_hat, pre = self._challenges_both(dK, messages, want_host=False, scope=scope, want_pre=True)
+            return dK, dC, c_hat, pre
+        if want_dev:
+            return (None,) + self._challenges_both(vk, messages, scope=scope)
+        with DeviceScope() as t:                            # hash_ag reads the host copy; nothing needs c_hat on the device
+            return (None, None) + self._challenges_both(vk, messages, scope=t)[1:]
+
+    def _alpha_hat_many_dev(self, scope, dK, dC, pre, L, R, off, valid=None):
+        """_alpha_hat_many on the device (fz_hash_ag_ragged_dev, a wave per committee): every group's keys sorted by str(vk) on
+        the host (one C call over all groups; the sort is stable, so the valid signers' order is that order filtered, as in
+        screened_alpha_coefficients), the prehashes uploaded, one call: -> dAl [sum N][d] in `scope`, zero rows for the signers
+        valid[i] leaves out.  dK [sum N][2][d] and dC [sum N][d] are read where they are: c_hat is not downloaded and no
+        coefficient is uploaded.  FusionHipError(FZ_E_UNSUPPORTED) for a parameter set the kernel does not cover."""
+        n = int(off[-1])
+        order = hostpipe.sort_by_vk_string_ragged(self.P, L, R, off, self.threads)
+        goff = np.asarray(off, dtype=np.int64)
+        if valid is not None:
+            keep = np.asarray(valid, dtype=bool).reshape(n)[order]
+            counts = np.add.reduceat(keep.astype(np.int64), goff[:-1]) if n else np.zeros(0, dtype=np.int64)
+            order = order[keep]
+            goff = np.concatenate([[0], np.cumsum(counts[counts > 0])]).astype(np.int64)
+        dP = self._up(scope, np.ascontiguousarray(pre, dtype=np.uint8).reshape(n, 32))
+        dAl = self._new(scope, (n, self.d))
+        self.ctx.hash_ag_ragged_dev(self.P, dK.ptr, dP.ptr, dC.ptr, n, order, goff, dAl.ptr)
+        return dAl
+
+    def hash_ag_many_dev(self, vk, messages, sizes, valid=None, scope=None):
+        """Everything the many-committee calls derive from the keys and messages of G committees (sizes = signers per committee,
+        concatenated as aggregate_many takes them), computed ON THE DEVICE: -> (dC [sum N][d] challenges c_hat, dAl [sum N][d]
+        aggregation coefficients alpha_hat, offsets [G + 1]), both in the callers' row order.  valid ([sum N] booleans, None:
+        all): hash_ag of each committee runs over its signers with valid[i] set, the others' rows of dAl are zero.  Only the
+        key sort runs on the host.  dC and dAl are the caller's to free, or with `scope` that DeviceScope's (as hash_ag_dev).
+        Raises FusionHipError(FZ_E_UNSUPPORTED) for parameter sets the kernel does not cover, whatever self.hash_ag says."""
+        if scope is None:
+            with DeviceScope() as tmp:
+                dC, dAl, off = self.hash_ag_many_dev(vk, messages, sizes, valid, tmp)
+                return tmp.release(dC), tmp.release(dAl), off
+        sizes = self._many_sizes(vk, messages, sizes)
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        dK = self._take(scope, vk, (int(off[-1]), 2, self.d))
+        _, L, R = self._split_vk(vk)
+        dC, _, pre = self._challenges_both(dK, messages, want_host=False, scope=scope, want_pre=True)
+        return dC, self._alpha_hat_many_dev(scope, dK, dC, pre, L, R, off, valid), off
+
+    def _alpha_hat_many(self, scope, off, L, R, pre, c_hat, valid=None, dK=None, dC=None):
         """hash_ag's coefficients for the G = len(off) - 1 independent aggregates of rows off[g]:off[g+1], over the signers with
-        valid[i] set (None: all): one host thread per aggregate for its sort + serial SHAKE-256 (the sponges are what bounds a
+        valid[i] set (None: all): -> dAl [sum N][d] in `scope`.  THE place where the many-committee calls branch on
+        self.hash_ag.  With dK (what _many_inputs returns for the device form): _alpha_hat_many_dev from dK and dC; its
+        FZ_E_UNSUPPORTED turns the device form off for this object and goes on here with a host copy of c_hat.  Host form: one
+        host thread per aggregate for its sort + serial SHAKE-256 (the sponges are what bounds a
         lone aggregate: independent aggregates hide each other's), zero rows without hashing for a group with no valid signer,
-        then ONE upload + transform of all rows: -> dAl [sum N][d] in `scope`"""
+        then ONE upload + transform of all rows."""
         from concurrent.futures import ThreadPoolExecutor
+        if dK is not None:
+            try:
+                return self._alpha_hat_many_dev(scope, dK, dC, pre, L, R, off, valid)
+            except FusionHipError as e:
+                if e.code != FZ_E_UNSUPPORTED:
+                    raise
+                self.device_hash_ag = False
+            if c_hat is None:
+                c_hat = dC.numpy()
         g = len(off) - 1
         per = max(1, self.threads // max(1, g))
 
@@ -852,8 +962,8 @@ class BatchScheme:
         the buffers in `scope`"""
         vk, L, R = self._split_vk(vk)
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        dC, c_hat, pre = self._challenges_both(vk, messages, scope=scope)
-        return dC, self._alpha_hat_many(scope, off, L, R, pre, c_hat), off, L, R
+        dK, dC, c_hat, pre = self._many_inputs(scope, vk, messages, sizes)
+        return dC, self._alpha_hat_many(scope, off, L, R, pre, c_hat, dK=dK, dC=dC), off, L, R
 
     def aggregate_many(self, vk, messages, sig, sizes):
         """G independent aggregate() calls (fusion.py:655; the reference is called once per aggregate) as one batch:
@@ -912,18 +1022,18 @@ class BatchScheme:
         with DeviceScope() as s:
             dB = self._records_dev(s, data, n, rb)
             dV = self._new(s, (n,))
+            dH = dC = None                                  # the keys and c_hat on the device, as hash_ag's device form reads them
             if screened:
                 dK = self._take(s, vk, (n, 2, self.d))
-                dC, c_hat, pre = self._challenges_both(dK, messages, scope=s)
+                dH, dC, c_hat, pre = self._many_inputs(s, dK, messages, sizes)
                 self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
             else:
                 self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
             _, L, R = self._split_vk(vk)
             if not screened:
-                with DeviceScope() as t:                    # hash_ag reads the host copy; nothing here needs c_hat on the device
-                    _, c_hat, pre = self._challenges_both(vk, messages, scope=t)
+                dH, dC, c_hat, pre = self._many_inputs(s, vk, messages, sizes, want_dev=False)
             codes = dV.numpy()
-            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, codes == 0)
+            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, codes == 0, dK=dH, dC=dC)
             dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
             self.ctx.aggregate_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, off, self.l, bound, dP.ptr, self.l * self.d, dO.ptr)
             out, extras = self._aggregates_out(s, dO, g, encoded)
@@ -982,11 +1092,11 @@ class BatchScheme:
             dV = self._new(s, (n,))
             self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
             dK = self._take(s, vk, (n, 2, self.d))
-            dC, c_hat, pre = self._challenges_both(dK, messages, scope=s)      # beside the check
+            dH, dC, c_hat, pre = self._many_inputs(s, dK, messages, sizes)     # beside the check
             _, L, R = self._split_vk(vk)
             codes = dV.numpy()
             valid = codes == 0
-            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, valid)
+            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, valid, dK=dH, dC=dC)
             dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
             dT, dW = self._new(s, (g, self.d), np.int64), self._new(s, (g,))
             self.ctx.aggregate_target_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, dK.ptr, dC.ptr, off, self.l, bound, dP.ptr,

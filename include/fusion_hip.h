@@ -545,6 +545,11 @@ FZ_API int fz_challenge_coefficients(const fz_scheme_params *P, const int32_t *h
  * i-th key in sorted order (stable). */
 FZ_API int fz_sort_by_vk_string(const fz_scheme_params *P, const int32_t *h_vk_left, const int32_t *h_vk_right,
                                 size_t N, size_t *h_order, int threads);
+/* the same for G independent groups in one call: group g = rows h_off[g] .. h_off[g + 1] - 1 of the two arrays; h_order[h_off[g] ..
+ * h_off[g + 1] - 1] receives that group's rows (indices into the whole arrays) in the order fz_sort_by_vk_string gives the
+ * group alone.  Entries of h_order below h_off[0] are not written.  FZ_E_BADARG for decreasing offsets. */
+FZ_API int fz_sort_by_vk_string_ragged(const fz_scheme_params *P, const int32_t *h_vk_left, const int32_t *h_vk_right,
+                                       const size_t *h_off, size_t G, size_t *h_order, int threads);
 /* hash_ag up to the NTTs (fusion.py:573-629): keys, pre-hashed messages and NTT-domain challenges c_hat
  * [N][degree], all already in sorted key order -> coefficient rows [N][degree] of the aggregation coefficients. */
 FZ_API int fz_aggregation_coefficients(const fz_scheme_params *P, const int32_t *h_vk_left,
@@ -563,7 +568,8 @@ FZ_API int fz_aggregation_coefficients(const fz_scheme_params *P, const int32_t 
  * once).  Only as many XOF bytes are squeezed as the decoder consumes (a prefix of the reference's n).  Supported: ternary
  * challenges (norm bound 1: both parameter sets of the reference), degree 4..256; otherwise FZ_E_UNSUPPORTED -- use
  * fz_challenge_coefficients.
- * hash_ag (fusion.py:632-652) stays on the host: it is ONE serial XOF over all signers by construction.
+ * hash_ag (fusion.py:632-652) of ONE committee stays on the host: it is one serial XOF over all signers by construction (many
+ * committees at once: fz_hash_ag_ragged_dev below).
  * (The entries: csrc/fz_staged_capi.hip, with the device sampler's below; the kernels: csrc/fz_challenge.hip.) */
 FZ_API int fz_challenge_coefficients_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash,
                                          size_t N, int32_t *d_coefs);
@@ -575,6 +581,29 @@ FZ_API int fz_challenge_hat_dev(fz_ctx *ctx, const fz_scheme_params *P, const in
  * (the call then synchronises the stream before it returns: the digests are the kernel's). */
 FZ_API int fz_challenge_hat_msgs_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const char *h_msgs,
                                      const size_t *h_msg_off, size_t N, int32_t *d_c_hat, uint8_t *h_prehash_out);
+
+/* ---- hash_ag for MANY committees on the device (csrc/fz_hash_ag.hip; the entry: csrc/fz_hash_ag_capi.hip) ---------------
+ * hash_vks_and_ints_and_challs with its transforms (fusion.py:573-652) for G independent committees in one launch, a wave per
+ * committee: the exact text str(list(zip(keys, pre-hashed messages, challenges))) behind agg_xof_dst + ",", one SHAKE-256 per
+ * committee, N_g sections of agg_coef_bytes bytes, the byte decoder (fusion.py:422-481; a shuffle draw whose bytes lie past
+ * the section takes 0, as the reference's empty slice does) and the forward transform.
+ * d_vk [N][2][degree], d_pre [N][32] (the SHA3-256 digests = the pre-hashed integers, little-endian) and d_c_hat [N][degree]
+ * (NTT domain, any int32) in the callers' row order, all in DEVICE memory; h_order [M] row indices and h_off [G + 1] offsets
+ * into h_order, in HOST memory (copied into pinned staging that the kernel reads in place; consumed when the call returns):
+ * committee g hashes rows h_order[h_off[g]] .. h_order[h_off[g + 1] - 1] in that order -- the caller has sorted them by str(vk)
+ * (fz_sort_by_vk_string) and left out whom it screens out.  d_alpha_hat [N][degree]: row h_order[i] receives the transform of
+ * the i-th decoded polynomial of its committee, every row not named stays ZERO.  h_off[G] (= M) is at most N.
+ * In this order: FZ_E_BADARG for a NULL context or parameters, a NULL pointer with N > 0 (h_off with G > 0, h_order with M > 0),
+ * parameters that do not belong to the context, a device pointer that is not 16-byte aligned (d_pre: 4-byte), graph capture, N
+ * or G of 2^31 or more, offsets that do not start at 0 or decrease, an empty committee, h_off[G] > N, an order entry >= N or
+ * named twice; FZ_E_UNSUPPORTED for anything but ternary coefficients (norm bound 1), degree 4..256 (a power of two), omega_ag <=
+ * min(64, degree), a section that would cut an index chunk, what the wave form of the challenge pipeline refuses, and a
+ * ring-only context -- use fz_aggregation_coefficients.  Nothing is enqueued and nothing written when a code is returned.  N == 0
+ * does nothing; G == 0 or M == 0 leaves N zero rows and launches no kernel.  Asynchronous on the context's stream, no host
+ * synchronisation. */
+FZ_API int fz_hash_ag_ragged_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *d_pre,
+                                 const int32_t *d_c_hat, size_t N, const uint32_t *h_order, const size_t *h_off, size_t G,
+                                 int32_t *d_alpha_hat);
 
 /* ---- reference-exact sampling on the host -----------------------------------------
  * CPython's MT19937 `random` exactly as the reference's samplers drive it (random.seed(int), randrange):
