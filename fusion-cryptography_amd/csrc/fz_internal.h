@@ -401,6 +401,9 @@ int fz_launch_challenge_wave(fz_ctx *ctx, const fz_scheme_params *P, const int32
 int fz_launch_prehash(fz_ctx *ctx, const fz_scheme_params *P, const uint8_t *d_msgs, const unsigned long long *d_off, size_t N,
                       uint8_t *d_pre, uint32_t *d_dec);          // d_dec [N][16]: the integers in base 10^9 + chunk count
 void fz_challenge_weight_table(int index_bytes, int degree, uint32_t *h_tab);      // (degree + 1) * 16 words
+// fz_challenge_hat_msgs_dev's pipeline with the digests left in device memory (fz_staged_capi.hip; the entry: fz_vk_order_capi.hip)
+int challenge_msgs_keep_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const char *h_msgs, const size_t *h_msg_off, size_t N,
+                            int32_t *d_c_hat, uint8_t *d_prehash_out);
 void fz_host_vk_text_parts(const fz_scheme_params *P, char *s0, int *n0, char *s1, int *n1, char *s2, int *n2, int cap);
 size_t fz_host_challenge_needed_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes);
 bool fz_host_params_ok(const fz_scheme_params *P);
@@ -414,6 +417,13 @@ int fz_launch_hash_ag(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_v
                       const uint32_t *ord, const void *grp, size_t G, const uint32_t *d_tab, int32_t *d_alpha);
 void fz_host_agg_text_parts(const fz_scheme_params *P, char *q0, char *q1, char *q2a, char *q2b, char *q3, int *n, int cap);
 size_t fz_host_agg_section_bytes(const fz_scheme_params *P, int *sign_bytes, int *coef_bytes, int *index_bytes);
+
+// the key sort of hash_ag for many committees on the device (fz_vk_order.hip; its entries: fz_vk_order_capi.hip)
+// grp [G] uint4 (first row, rows >= 1, first entry of d_order, 0) and valid (a byte per row, or NULL: all), both device-visible;
+// d_order: per committee the global indices of its rows with valid set, in the text order of str(vk), stable
+int fz_launch_vk_order(fz_ctx *ctx, const int32_t *d_vk, int degree, const void *grp, size_t G, const uint8_t *valid, uint32_t *d_order);
+// d_vk [N][2][degree] -> d_left [N][degree], d_right [N][degree] (degree a power of two >= 4, 16-byte aligned pointers)
+int fz_launch_vk_halves(fz_ctx *ctx, const int32_t *d_vk, size_t N, int degree, int32_t *d_left, int32_t *d_right);
 
 // launchers of the streaming kernels (fz_pointwise.hip; fz_launch_aggregate: fz_aggregate.hip)
 int fz_launch_fill_synthetic(fz_ctx *ctx, int32_t *out, size_t count, unsigned long long seed);

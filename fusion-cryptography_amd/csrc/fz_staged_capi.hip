@@ -15,6 +15,7 @@
 struct ChalCall {
     fz_ctx *ctx; const fz_scheme_params *P; const int32_t *d_vk; const uint8_t *h_prehash; const char *h_msgs; const size_t *h_msg_off;
     uint8_t *h_prehash_out; size_t N; int32_t *d_out; bool transform;         // what the entry was handed
+    uint8_t *d_prehash_out;                              // ... (with messages only) the digests stay in DEVICE memory: nothing waits for them
     size_t text_stride; int out_blocks, index_bytes;     // challenge_geometry: bytes of a signer's text row, blocks of SHAKE output, the decoder's index bytes
     const uint32_t *d_tab;                               // challenge_table
 };
@@ -76,7 +77,8 @@ static int challenge_wave_form(const ChalCall &c) {
         if (msg_bytes) memcpy(st->h + o_msg, c.h_msgs + c.h_msg_off[0], msg_bytes);
     }
     int rc = fz_launch_challenge_wave(ctx, c.P, c.d_vk, c.h_prehash ? st->h + o_pre : nullptr, st->h + o_msg, (const unsigned long long *)(st->h + o_off),
-                                      digests_out ? st->h + o_pre : nullptr, N, c.text_stride, c.out_blocks, c.d_tab, c.d_out);
+                                      c.d_prehash_out ? c.d_prehash_out : digests_out ? st->h + o_pre : nullptr, N, c.text_stride, c.out_blocks, c.d_tab,
+                                      c.d_out);
     if (rc == FZ_OK && c.transform) rc = fz_launch_ntt(ctx, c.d_out, c.d_out, N, false);
     FZ_TRY(stage_release(ctx, st, rc));
     if (digests_out) {
@@ -104,18 +106,19 @@ static int challenge_chunked_form(const ChalCall &c) {
         const size_t o_msg = s.take_packed(msg_bytes);        // (64-aligned)
         FZ_TRY(s.fit(ctx, c.h_prehash ? with_digests : s.next));
         uint8_t *sp = s.at<uint8_t>(0);
+        uint8_t *pre = c.d_prehash_out ? c.d_prehash_out + 32 * base : sp + o_pre;      // (the caller's digests are written where they stay)
         if (c.h_prehash) {
-            FZ_HIP(hipMemcpyAsync(sp + o_pre, c.h_prehash + 32 * base, n * 32, hipMemcpyHostToDevice, ctx->stream), "upload of the pre-hashed messages");
+            FZ_HIP(hipMemcpyAsync(pre, c.h_prehash + 32 * base, n * 32, hipMemcpyHostToDevice, ctx->stream), "upload of the pre-hashed messages");
         } else {
             FZ_HIP(hipMemcpyAsync(sp + o_off, c.h_msg_off + base, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream), "upload of the message offsets");
             if (msg_bytes)
                 FZ_HIP(hipMemcpyAsync(sp + o_msg, c.h_msgs + c.h_msg_off[base], msg_bytes, hipMemcpyHostToDevice, ctx->stream), "upload of the messages");
-            FZ_TRY(fz_launch_prehash(ctx, c.P, sp + o_msg, (const unsigned long long *)(sp + o_off), n, sp + o_pre, (uint32_t *)(sp + o_dec)));
+            FZ_TRY(fz_launch_prehash(ctx, c.P, sp + o_msg, (const unsigned long long *)(sp + o_off), n, pre, (uint32_t *)(sp + o_dec)));
             if (c.h_prehash_out)
-                FZ_HIP(hipMemcpyAsync(c.h_prehash_out + 32 * base, sp + o_pre, n * 32, hipMemcpyDeviceToHost, ctx->stream), "download of the pre-hashed messages");
+                FZ_HIP(hipMemcpyAsync(c.h_prehash_out + 32 * base, pre, n * 32, hipMemcpyDeviceToHost, ctx->stream), "download of the pre-hashed messages");
         }
         FZ_HIP(hipStreamSynchronize(ctx->stream), "upload sync");      // the caller's buffers have been consumed when this returns
-        FZ_TRY(fz_launch_challenge(ctx, c.P, c.d_vk + base * 2 * (size_t)c.P->degree, sp + o_pre,
+        FZ_TRY(fz_launch_challenge(ctx, c.P, c.d_vk + base * 2 * (size_t)c.P->degree, pre,
                                    c.h_prehash ? nullptr : (const uint32_t *)(sp + o_dec), n, sp + o_text, c.text_stride,
                                    (int *)(sp + o_nb), (uint32_t *)(sp + o_xof), xstride, c.out_blocks, c.d_tab,
                                    c.d_out + base * (size_t)c.P->degree));
@@ -125,8 +128,8 @@ static int challenge_chunked_form(const ChalCall &c) {
 }
 
 static int challenge_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *h_prehash, const char *h_msgs,
-                         const size_t *h_msg_off, uint8_t *h_prehash_out, size_t N, int32_t *d_out, bool transform) {
-    ChalCall c{ctx, P, d_vk, h_prehash, h_msgs, h_msg_off, h_prehash_out, N, d_out, transform, 0, 0, 0, nullptr};
+                         const size_t *h_msg_off, uint8_t *h_prehash_out, size_t N, int32_t *d_out, bool transform, uint8_t *d_prehash_out = nullptr) {
+    ChalCall c{ctx, P, d_vk, h_prehash, h_msgs, h_msg_off, h_prehash_out, N, d_out, transform, d_prehash_out, 0, 0, 0, nullptr};
     FZ_TRY(challenge_checks(c));
     if (N == 0) return FZ_OK;
     FZ_TRY(challenge_geometry(c));
@@ -137,6 +140,13 @@ static int challenge_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *
     constexpr size_t kWaveFormMax = 4608;                    // 4096 signers: 0.67 ms against 0.77; 5120: 0.85 against 0.79
     const bool wave_form = fz_challenge_wave_ok(P) && (ctx->knob_shake_full == 3 || (ctx->knob_shake_full == 0 && N <= kWaveFormMax));
     return wave_form ? challenge_wave_form(c) : challenge_chunked_form(c);
+}
+
+// fz_challenge_hat_msgs_dev with the digests left in DEVICE memory (d_prehash_out [N][32]): what fz_challenge_hat_msgs_keep_dev
+// (fz_vk_order_capi.hip, with the entries that read the digests there) runs -- the one copy of the rules above serves it too
+int challenge_msgs_keep_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const char *h_msgs, const size_t *h_msg_off, size_t N,
+                            int32_t *d_c_hat, uint8_t *d_prehash_out) {
+    return challenge_dev(ctx, P, d_vk, nullptr, h_msgs, h_msg_off, nullptr, N, d_c_hat, true, d_prehash_out);
 }
 
 extern "C" {

@@ -1,5 +1,5 @@
 // fz_staged_rules.h -- what the host units that take small host inputs through the context's pinned staging slots share
-// (fz_staged_capi.hip, fz_hash_ag_capi.hip), written once: the slots' protocol and the challenge decoder's cached weight table.
+// (fz_staged_capi.hip, fz_hash_ag_capi.hip, fz_vk_order_capi.hip), written once: the slots' protocol and the challenge decoder's cached weight table.
 // Host code only; everything is private to the unit that includes it.
 #ifndef FZ_STAGED_RULES_H
 #define FZ_STAGED_RULES_H

@@ -787,9 +787,10 @@ def _groups_for_many(params: Params, keys_per_group, messages_per_group):
             [m for ms in messages_per_group for m in ms], [len(ks) for ks in keys_per_group])
 
 
-def _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, verify, hash_ag="host"):
+def _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, verify, hash_ag="host", key_sort="host"):
     """aggregate_many_from_bytes (verify=False: no verdicts, None) and aggregate_verify_many_from_bytes: -> ([Signature] * G, verdicts);
-    hash_ag: BatchScheme's, where the committees' aggregation coefficients are hashed ("host", "device" or "auto")"""
+    hash_ag: BatchScheme's, where the committees' aggregation coefficients are hashed ("host", "device" or "auto"); key_sort:
+    BatchScheme's, where the device form sorts the committees' keys ("host" or "device")"""
     from fusion_hip import ENCODING_REASONS
     from fusion_hip.scheme import BatchScheme, encoded_size
     if len(blobs_per_group) != len(keys_per_group):
@@ -804,7 +805,7 @@ def _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs
                 raise ValueError(f"group {g} record {i}: a 'signature' record is {size} bytes, not {len(b)}")
     if not sizes:
         return [], ([] if verify else None)
-    bs = BatchScheme(params, hash_ag=hash_ag)
+    bs = BatchScheme(params, hash_ag=hash_ag, key_sort=key_sort)
     try:
         call = bs.aggregate_verify_many_encoded if verify else bs.aggregate_many_encoded
         out, codes, *verdicts = call(vk_rows(), messages, b"".join(bytes(b) for blobs in blobs_per_group for b in blobs), sizes)
@@ -819,33 +820,37 @@ def _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs
 
 
 def aggregate_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],
-                              blobs_per_group: List[List[bytes]], hash_ag: str = "host") -> List[Signature]:
+                              blobs_per_group: List[List[bytes]], hash_ag: str = "host", key_sort: str = "host") -> List[Signature]:
     """NOT in the reference: aggregate_from_bytes for G committees at once -> [Signature] * G, entry g what
     aggregate_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs_per_group[g]) returns
     (BatchScheme.aggregate_many_encoded: one launch over all committees' bytes).  Raises ValueError, naming the group and the
     record, for unequal numbers of groups, of keys, messages and blobs of a group, for a group without signers, for a blob of
     the wrong length and for a record that is not canonical (the first one, with the reason).  hash_ag: where the committees'
-    aggregation coefficients are hashed, "host" (the default), "device" or "auto" (BatchScheme's option; the result is the same)."""
-    return _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, False, hash_ag)[0]
+    aggregation coefficients are hashed, "host" (the default), "device" or "auto" (BatchScheme's option; the result is the same).
+    key_sort: where the device form sorts each committee's keys, "host" (the default) or "device" (BatchScheme's option; the
+    result is the same)."""
+    return _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, False, hash_ag, key_sort)[0]
 
 
 def aggregate_verify_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]],
                                      messages_per_group: List[List[str]],
                                      blobs_per_group: List[List[bytes]],
-                                     hash_ag: str = "host") -> Tuple[List[Signature], List[Tuple[bool, str]]]:
+                                     hash_ag: str = "host",
+                                     key_sort: str = "host") -> Tuple[List[Signature], List[Tuple[bool, str]]]:
     """NOT in the reference: aggregate_verify_from_bytes for G committees at once -> ([Signature] * G, [(ok, reason)] * G), entry g
     of each what aggregate_verify_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs_per_group[g]) returns
     (BatchScheme.aggregate_verify_many_encoded: one launch for all committees' aggregates and verification targets, one for all
-    verdicts).  Raises ValueError as aggregate_many_from_bytes does; hash_ag as there."""
-    return _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, True, hash_ag)
+    verdicts).  Raises ValueError as aggregate_many_from_bytes does; hash_ag and key_sort as there."""
+    return _aggregate_many_from_bytes(params, keys_per_group, messages_per_group, blobs_per_group, True, hash_ag, key_sort)
 
 
 def verify_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVerificationKey]], messages_per_group: List[List[str]],
-                           blobs: List[bytes], hash_ag: str = "host") -> List[Tuple[bool, str]]:
+                           blobs: List[bytes], hash_ag: str = "host", key_sort: str = "host") -> List[Tuple[bool, str]]:
     """NOT in the reference: verify_from_bytes for G aggregates at once (blobs[g]: the "aggregate" record of group g) ->
     [(ok, reason)] * G, entry g what verify_from_bytes(params, keys_per_group[g], messages_per_group[g], blobs[g]) returns
     (BatchScheme.verify_many_encoded).  Raises ValueError, naming the group, for unequal numbers of groups, of keys and messages
-    of a group, for a group without signers and for a blob of the wrong length.  hash_ag as aggregate_many_from_bytes takes it."""
+    of a group, for a group without signers and for a blob of the wrong length.  hash_ag and key_sort as aggregate_many_from_bytes
+    takes them."""
     from fusion_hip.scheme import BatchScheme, encoded_size
     if len(blobs) != len(keys_per_group):
         raise ValueError(f"{len(keys_per_group)} groups of keys, {len(blobs)} records")
@@ -856,7 +861,7 @@ def verify_many_from_bytes(params: Params, keys_per_group: List[List[OneTimeVeri
             raise ValueError(f"group {g} record 0: an 'aggregate' record is {size} bytes, not {len(b)}")
     if not sizes:
         return []
-    bs = BatchScheme(params, hash_ag=hash_ag)
+    bs = BatchScheme(params, hash_ag=hash_ag, key_sort=key_sort)
     try:
         return bs.verify_many_encoded(vk_rows(), messages, b"".join(bytes(b) for b in blobs), sizes)
     finally:

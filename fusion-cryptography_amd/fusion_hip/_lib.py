@@ -163,6 +163,10 @@ SIGNATURES.update({
     "fz_challenge_hat_dev": (c_int, [_ctx, _spp, c_void_p, _u8p, c_size_t, c_void_p]),
     "fz_challenge_hat_msgs_dev": (c_int, [_ctx, _spp, c_void_p, c_char_p, _szp, c_size_t, c_void_p, _u8p]),
     "fz_hash_ag_ragged_dev": (c_int, [_ctx, _spp, c_void_p, c_void_p, c_void_p, c_size_t, _u32p, _szp, c_size_t, c_void_p]),
+    "fz_sort_by_vk_string_ragged_dev": (c_int, [_ctx, _spp, c_void_p, c_size_t, _szp, c_size_t, _u8p, c_void_p]),
+    "fz_hash_ag_ragged_sorted_dev": (c_int, [_ctx, _spp, c_void_p, c_void_p, c_void_p, c_size_t, _szp, c_size_t, _u8p, c_void_p]),
+    "fz_challenge_hat_msgs_keep_dev": (c_int, [_ctx, _spp, c_void_p, c_char_p, _szp, c_size_t, c_void_p, c_void_p]),
+    "fz_vk_halves_async": (c_int, [_ctx, c_void_p, c_size_t, c_void_p, c_void_p]),
     "fz_sample_ntt_values": (c_int, [ctypes.c_uint64, c_int64, c_int, _i32p]),
     "fz_sample_coefficients": (c_int, [ctypes.c_uint64, c_int64, c_int, c_int64, c_int64, _i32p]),
     "fz_sample_coefficients_state": (c_int, [ctypes.c_uint64, c_int64, c_int, c_int64, c_int64, _i32p, _u32p]),

@@ -303,6 +303,54 @@ class Context:
             order.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), off.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
             off.shape[0] - 1, c_void_p(d_alpha_hat or None)))
 
+    @staticmethod
+    def _groups(offsets, valid):
+        """offsets [G + 1] as uintp and the optional mask as uint8 with its pointer (NULL without one)"""
+        off = np.ascontiguousarray(offsets, dtype=np.uintp).reshape(-1)
+        if off.shape[0] < 1:
+            raise FusionHipError(FZ_E_BADARG, "offsets need at least one entry")
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        if valid is None:
+            return off, None, ctypes.cast(None, u8p)
+        ok = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, dtype=np.uint8)
+        if ok.shape[0] != int(off[-1]):
+            raise FusionHipError(FZ_E_BADARG, f"{ok.shape[0]} mask entries, offsets end at {int(off[-1])}")
+        return off, ok, ok.ctypes.data_as(u8p)
+
+    def sort_by_vk_string_ragged_dev(self, P, d_vk, N, offsets, valid, d_order):
+        """the key sort of hash_ag for len(offsets) - 1 committees on the device, a wave per committee
+        (fz_sort_by_vk_string_ragged_dev): d_vk [N][2][d] (device), offsets [G + 1] from 0 to N, valid [N] booleans or None (all);
+        d_order (device, uint32) receives each committee's valid rows, as global indices, in the order sorted(key=str) puts
+        their keys, compacted committee after committee.  Asynchronous; offsets and valid are consumed when the call returns."""
+        off, ok, okp = self._groups(offsets, valid)
+        check(self._lib, self._lib.fz_sort_by_vk_string_ragged_dev(
+            self._h, byref(P), c_void_p(d_vk or None), N, off.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), off.shape[0] - 1, okp,
+            c_void_p(d_order or None)))
+
+    def hash_ag_ragged_sorted_dev(self, P, d_vk, d_pre, d_c_hat, N, offsets, valid, d_alpha_hat):
+        """hash_ag_ragged_dev with the key sort on the device (fz_hash_ag_ragged_sorted_dev): committee g hashes its rows
+        offsets[g]:offsets[g + 1] with valid set (None: all) in the order of str(vk); d_alpha_hat [N][d] receives what
+        hash_ag_ragged_dev writes for the host sort's order, bit for bit.  Asynchronous; offsets and valid are consumed when the
+        call returns."""
+        off, ok, okp = self._groups(offsets, valid)
+        check(self._lib, self._lib.fz_hash_ag_ragged_sorted_dev(
+            self._h, byref(P), c_void_p(d_vk or None), c_void_p(d_pre or None), c_void_p(d_c_hat or None), N,
+            off.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), off.shape[0] - 1, okp, c_void_p(d_alpha_hat or None)))
+
+    def challenge_msgs_keep_dev(self, P, d_vk, blob, offsets, N, d_out, d_prehash):
+        """challenge_msgs_dev with the digests left on the device (fz_challenge_hat_msgs_keep_dev): d_prehash [N][32] uint8
+        (device) receives them, and nothing waits for them"""
+        off = np.ascontiguousarray(offsets, dtype=np.uintp)
+        if off.shape[0] != N + 1:
+            raise FusionHipError(FZ_E_BADARG, f"{off.shape[0]} offsets for {N} messages")
+        check(self._lib, self._lib.fz_challenge_hat_msgs_keep_dev(
+            self._h, byref(P), c_void_p(d_vk or None), blob, off.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)), N, c_void_p(d_out or None),
+            c_void_p(d_prehash or None)))
+
+    def vk_halves_dev(self, d_vk, N, d_left, d_right):
+        """keys [N][2][d] taken apart on the device (fz_vk_halves_async): d_left [N][d], d_right [N][d]"""
+        check(self._lib, self._lib.fz_vk_halves_async(self._h, c_void_p(d_vk or None), N, c_void_p(d_left or None), c_void_p(d_right or None)))
+
     def pw_dev(self, op, d_a, d_b, d_out, count):
         fn = {OP_MUL: self._lib.fz_pw_mul, OP_ADD: self._lib.fz_pw_add, OP_SUB: self._lib.fz_pw_sub}[op]
         check(self._lib, fn(self._h, c_void_p(d_a), c_void_p(d_b), c_void_p(d_out), count))

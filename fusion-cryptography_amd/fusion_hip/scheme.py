@@ -116,6 +116,7 @@ def screened_alpha_coefficients(P, L, R, pre, c_hat, valid=None, threads=None, o
 # committee costs the calling thread in Python.  All constants are medians of profiles/r25_hash_ag_many.txt (MI355X, 16
 # threads), which also shows the rule picking the faster form in every cell it measures.
 _HASH_AG_FORMS = ("host", "device", "auto")
+_KEY_SORT_FORMS = ("host", "device")          # BatchScheme(key_sort=...): where the device form of hash_ag sorts each committee's keys
 _HASH_AG_PERMS = {128: 30, 256: 99}           # per signer: (item text + section) / 136 (tools/probes/hash_ag_many.py)
 _HASH_AG_SIMDS, _HASH_AG_WAVES = 1024, 4      # 256 CUs x 4 SIMDs; the kernel's waves per SIMD (127 registers, 26 KB LDS per workgroup)
 _HASH_AG_DEVICE_US = 2.65                     # profiles/r25_hash_ag_many.txt: 64 x 64 at secpar 256, 16.81 ms / (64 x 99.2)
@@ -128,14 +129,19 @@ _HASH_AG_DEVICE_CALL_US = (500.0, 0.02)       # ... device - entry: 0.5 ms per c
 class BatchScheme:
     hash_ag = "host"                     # (the defaults of an object made without __init__)
     device_hash_ag = True
+    key_sort = "host"
 
-    def __init__(self, params, device=0, threads=None, private_context=False, hash_ag="host"):
+    def __init__(self, params, device=0, threads=None, private_context=False, hash_ag="host", key_sort="host"):
         """params: a fusion.fusion.Params (or any object with the same attributes).
         hash_ag: where the many-committee calls (aggregate_many, verify_many and their _encoded forms) hash the committees'
         aggregation coefficients: "host" (the default: one host thread per committee), "device" (one wave per committee,
         fz_hash_ag_ragged_dev: c_hat is not downloaded and the coefficients are not uploaded) or "auto" (the device form where
         it covers the parameter set and is predicted faster for the call's committee sizes).  The results are the same bit for
         bit; a parameter set the device form does not cover falls back to the host once and stays there.
+        key_sort: where the DEVICE form of hash_ag sorts each committee's keys by str(vk): "host" (the default: one C call over a
+        host copy of the keys, fz_sort_by_vk_string_ragged) or "device" (a wave per committee, fz_hash_ag_ragged_sorted_dev: keys
+        that live on the device are not downloaded, the messages' digests stay on the device, and the call does not wait for
+        either).  It has no effect where hash_ag takes its host form.  The results are the same bit for bit.
         private_context: give this object a context and a HIP stream of its own instead of the process-wide one per device.
         A context serves one host thread at a time (include/fusion_hip.h), so several BatchSchemes that are to work
         CONCURRENTLY -- one per worker thread -- each need their own.  That is how batches of the BASELINE size keep the chip
@@ -144,6 +150,8 @@ class BatchScheme:
         close() releases the private context."""
         if hash_ag not in _HASH_AG_FORMS:
             raise FusionHipError(FZ_E_BADARG, f"hash_ag={hash_ag!r}: one of {_HASH_AG_FORMS}")
+        if key_sort not in _KEY_SORT_FORMS:
+            raise FusionHipError(FZ_E_BADARG, f"key_sort={key_sort!r}: one of {_KEY_SORT_FORMS}")
         self.params = params
         self.P = hostpipe.scheme_params(params)
         self.threads = threads or hostpipe.default_threads()
@@ -158,6 +166,7 @@ class BatchScheme:
             self.ctx = get_context(params.modulus, params.degree, params.root, params.inv_root, device)
         self.hash_ag = hash_ag           # where the many-committee calls hash their coefficients (_hash_ag_form)
         self.device_hash_ag = True       # ... its device form covers the parameter set (off after its first FZ_E_UNSUPPORTED)
+        self.key_sort = key_sort         # ... and where that form sorts the committees' keys (_keys_stay)
         self.device_hash = True          # per-signer challenge pipeline on the device (falls back to the host if unsupported)
         self.device_sampler = True       # secret polynomials sampled on the device (the same fallback)
         self.A = np.array([z.values for row in params.public_challenge.matrix for z in row], dtype=np.int32)
@@ -881,20 +890,78 @@ class BatchScheme:
         upload before), the host copies of c_hat and the prehashes, and dC unless want_dev is False."""
         if self._hash_ag_form(sizes) == "device":
             dK = self._take(scope, vk, (int(sum(sizes)), 2, self.d))
-            dC, c_hat, pre = self._challenges_both(dK, messages, want_host=False, scope=scope, want_pre=True)
-            return dK, dC, c_hat, pre
+            return (dK,) + self._challenges_keep(scope, dK, messages)
         if want_dev:
             return (None,) + self._challenges_both(vk, messages, scope=scope)
         with DeviceScope() as t:                            # hash_ag reads the host copy; nothing needs c_hat on the device
             return (None, None) + self._challenges_both(vk, messages, scope=t)[1:]
+
+    def _keys_stay(self, sizes):
+        """does the call over committees of `sizes` sort their keys on the device (key_sort="device" under the device form of
+        hash_ag)?  Then nothing needs a host copy of the keys: L and R are None from here on."""
+        return self.key_sort == "device" and self._hash_ag_form(sizes) == "device"
+
+    def _challenges_keep(self, scope, dK, messages):
+        """the challenge pass in front of hash_ag's device form: -> (dC [N][d] in `scope`, None, the digests [N][32]).  As it was:
+        c_hat stays on the device, the digests come back.  key_sort="device": the digests stay on the device too, a DeviceArray
+        in `scope` (fz_challenge_hat_msgs_keep_dev: nothing is downloaded and nothing waited for); a parameter set the device
+        pipeline does not cover takes the host pipeline as everywhere (_challenges_both)"""
+        if self.key_sort == "device" and self.device_hash:
+            n = len(messages)
+            blob, moff = hostpipe._pack_messages(messages)
+            dC, dP = self._new(scope, (n, self.d)), self._new(scope, (n, 32), np.uint8)
+            try:
+                self.ctx.challenge_msgs_keep_dev(self.P, dK.ptr, blob, moff, n, dC.ptr, dP.ptr)
+                return dC, None, dP
+            except FusionHipError as e:
+                if e.code != FZ_E_UNSUPPORTED:
+                    raise
+                self.device_hash = False
+        return self._challenges_both(dK, messages, want_host=False, scope=scope, want_pre=True)
+
+    def _halves_dev(self, scope, L, R, dK):
+        """the keys' halves as two device arrays [N][d]: uploads of the host copies, or -- the keys stayed on the device
+        (_keys_stay: L is None) -- dK [N][2][d] taken apart there"""
+        if L is not None:
+            return self._up(scope, L), self._up(scope, R)
+        n = dK.shape[0]
+        dL, dR = self._new(scope, (n, self.d)), self._new(scope, (n, self.d))
+        self.ctx.vk_halves_dev(dK.ptr, n, dL.ptr, dR.ptr)
+        return dL, dR
+
+    def sort_keys_many_dev(self, vk, sizes, valid=None):
+        """the order in which hash_ag hashes the keys of G committees (sizes = keys per committee, concatenated), computed ON THE
+        DEVICE (fz_sort_by_vk_string_ragged_dev, a wave per committee): -> int64 row indices into vk [sum N][2][d] (numpy or
+        DeviceArray), committee after committee, each committee's rows with valid[i] set (None: all) in the order
+        sorted(key=str) puts their keys -- hostpipe.sort_by_vk_string_ragged's order, filtered."""
+        sizes = [int(x) for x in sizes]
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        n = int(off[-1])
+        if any(x < 0 for x in sizes) or n != self._signer_count(vk):
+            raise FusionHipError(FZ_E_BADARG, f"sizes sum to {n} but {self._signer_count(vk)} keys were given")
+        m = n if valid is None else int(np.count_nonzero(np.asarray(valid).reshape(n)))
+        if m == 0:
+            return np.zeros(0, dtype=np.int64)
+        with DeviceScope() as s:
+            dK = self._take(s, vk, (n, 2, self.d))
+            dO = self._new(s, (n,), np.uint32)
+            self.ctx.sort_by_vk_string_ragged_dev(self.P, dK.ptr, n, off, valid, dO.ptr)
+            return dO.numpy()[:m].astype(np.int64)
 
     def _alpha_hat_many_dev(self, scope, dK, dC, pre, L, R, off, valid=None):
         """_alpha_hat_many on the device (fz_hash_ag_ragged_dev, a wave per committee): every group's keys sorted by str(vk) on
         the host (one C call over all groups; the sort is stable, so the valid signers' order is that order filtered, as in
         screened_alpha_coefficients), the prehashes uploaded, one call: -> dAl [sum N][d] in `scope`, zero rows for the signers
         valid[i] leaves out.  dK [sum N][2][d] and dC [sum N][d] are read where they are: c_hat is not downloaded and no
-        coefficient is uploaded.  FusionHipError(FZ_E_UNSUPPORTED) for a parameter set the kernel does not cover."""
+        coefficient is uploaded.  FusionHipError(FZ_E_UNSUPPORTED) for a parameter set the kernel does not cover.
+        key_sort="device": the sort runs on the device as well (fz_hash_ag_ragged_sorted_dev; L and R are not looked at), and
+        digests that are on the device already (pre a DeviceArray, _challenges_keep) are read where they are."""
         n = int(off[-1])
+        if self.key_sort == "device":
+            dP = pre if isinstance(pre, DeviceArray) else self._up(scope, np.ascontiguousarray(pre, dtype=np.uint8).reshape(n, 32))
+            dAl = self._new(scope, (n, self.d))
+            self.ctx.hash_ag_ragged_sorted_dev(self.P, dK.ptr, dP.ptr, dC.ptr, n, off, valid, dAl.ptr)
+            return dAl
         order = hostpipe.sort_by_vk_string_ragged(self.P, L, R, off, self.threads)
         goff = np.asarray(off, dtype=np.int64)
         if valid is not None:
@@ -912,7 +979,8 @@ class BatchScheme:
         concatenated as aggregate_many takes them), computed ON THE DEVICE: -> (dC [sum N][d] challenges c_hat, dAl [sum N][d]
         aggregation coefficients alpha_hat, offsets [G + 1]), both in the callers' row order.  valid ([sum N] booleans, None:
         all): hash_ag of each committee runs over its signers with valid[i] set, the others' rows of dAl are zero.  Only the
-        key sort runs on the host.  dC and dAl are the caller's to free, or with `scope` that DeviceScope's (as hash_ag_dev).
+        key sort runs on the host, and with key_sort="device" not even that: the keys are then not downloaded and the digests
+        stay on the device.  dC and dAl are the caller's to free, or with `scope` that DeviceScope's (as hash_ag_dev).
         Raises FusionHipError(FZ_E_UNSUPPORTED) for parameter sets the kernel does not cover, whatever self.hash_ag says."""
         if scope is None:
             with DeviceScope() as tmp:
@@ -921,8 +989,10 @@ class BatchScheme:
         sizes = self._many_sizes(vk, messages, sizes)
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         dK = self._take(scope, vk, (int(off[-1]), 2, self.d))
-        _, L, R = self._split_vk(vk)
-        dC, _, pre = self._challenges_both(dK, messages, want_host=False, scope=scope, want_pre=True)
+        L = R = None
+        if self.key_sort != "device":
+            _, L, R = self._split_vk(vk)
+        dC, _, pre = self._challenges_keep(scope, dK, messages)
         return dC, self._alpha_hat_many_dev(scope, dK, dC, pre, L, R, off, valid), off
 
     def _alpha_hat_many(self, scope, off, L, R, pre, c_hat, valid=None, dK=None, dC=None):
@@ -943,6 +1013,10 @@ class BatchScheme:
                 self.device_hash_ag = False
             if c_hat is None:
                 c_hat = dC.numpy()
+            if L is None:                                   # (the keys and the digests stayed on the device for the form that refused)
+                _, L, R = self._split_vk(dK)
+            if isinstance(pre, DeviceArray):
+                pre = pre.numpy()
         g = len(off) - 1
         per = max(1, self.threads // max(1, g))
 
@@ -958,12 +1032,14 @@ class BatchScheme:
 
     def _hash_ag_many(self, scope, vk, messages, sizes):
         """hash_ag for G independent aggregates whose signers are concatenated (aggregate g = rows off[g]:off[g+1]; sizes as
-        _many_sizes passed them): ONE device pass for all challenges, _alpha_hat_many.  -> (dC, dAl [sum N][d], offsets, L, R),
-        the buffers in `scope`"""
-        vk, L, R = self._split_vk(vk)
+        _many_sizes passed them): ONE device pass for all challenges, _alpha_hat_many.  -> (dC, dAl [sum N][d], offsets, L, R,
+        dK), the buffers in `scope`; L and R are None where the keys stay on the device (_keys_stay: _halves_dev takes dK)"""
+        L = R = None
+        if not self._keys_stay(sizes):
+            vk, L, R = self._split_vk(vk)
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         dK, dC, c_hat, pre = self._many_inputs(scope, vk, messages, sizes)
-        return dC, self._alpha_hat_many(scope, off, L, R, pre, c_hat, dK=dK, dC=dC), off, L, R
+        return dC, self._alpha_hat_many(scope, off, L, R, pre, c_hat, dK=dK, dC=dC), off, L, R, dK
 
     def aggregate_many(self, vk, messages, sig, sizes):
         """G independent aggregate() calls (fusion.py:655; the reference is called once per aggregate) as one batch:
@@ -972,7 +1048,7 @@ class BatchScheme:
         aggregate(params, keys_g, messages_g, signatures_g).signature_hat.  One launch for all aggregates."""
         sizes = self._many_sizes(vk, messages, sizes)
         with DeviceScope() as s:
-            dC, dAl, off, _, _ = self._hash_ag_many(s, vk, messages, sizes)
+            dC, dAl, off, _, _, _ = self._hash_ag_many(s, vk, messages, sizes)
             g = len(off) - 1
             dS = self._take(s, sig, (int(off[-1]), self.l, self.d))
             dO = self._new(s, (g, self.l, self.d))
@@ -989,8 +1065,8 @@ class BatchScheme:
             return out
         sizes = self._many_sizes(vk, messages, sizes)
         with DeviceScope() as s:
-            dC, dAl, off, L, R = self._hash_ag_many(s, vk, messages, sizes)
-            dL, dR = self._up(s, L), self._up(s, R)
+            dC, dAl, off, L, R, dK = self._hash_ag_many(s, vk, messages, sizes)
+            dL, dR = self._halves_dev(s, L, R, dK)
             dS = self._take(s, aggregates, (g, self.l, self.d))
             dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, dC, dAl, off)
             self.ctx.verify_with_target_batch_async_dev(self._A_dev().ptr, dS.ptr, dT.ptr, g, self.l, int(self.params.beta_vf),
@@ -1029,7 +1105,9 @@ class BatchScheme:
                 self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
             else:
                 self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
-            _, L, R = self._split_vk(vk)
+            L = R = None
+            if not self._keys_stay(sizes):
+                _, L, R = self._split_vk(vk)
             if not screened:
                 dH, dC, c_hat, pre = self._many_inputs(s, vk, messages, sizes, want_dev=False)
             codes = dV.numpy()
@@ -1093,7 +1171,9 @@ class BatchScheme:
             self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
             dK = self._take(s, vk, (n, 2, self.d))
             dH, dC, c_hat, pre = self._many_inputs(s, dK, messages, sizes)     # beside the check
-            _, L, R = self._split_vk(vk)
+            L = R = None
+            if dH is None or self.key_sort != "device":
+                _, L, R = self._split_vk(vk)
             codes = dV.numpy()
             valid = codes == 0
             dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, valid, dK=dH, dC=dC)
@@ -1143,8 +1223,8 @@ class BatchScheme:
         if out is not None:
             return out
         with DeviceScope() as s:
-            dC, dAl, off, L, R = self._hash_ag_many(s, vk, messages, sizes)
-            dL, dR = self._up(s, L), self._up(s, R)
+            dC, dAl, off, L, R, dK = self._hash_ag_many(s, vk, messages, sizes)
+            dL, dR = self._halves_dev(s, L, R, dK)
             dB = self._records_dev(s, data, g, rb)
             dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, dC, dAl, off)
             self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, g, self.l, bound, dT.ptr, 0, 0, dV.ptr)

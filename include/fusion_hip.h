@@ -605,6 +605,39 @@ FZ_API int fz_hash_ag_ragged_dev(fz_ctx *ctx, const fz_scheme_params *P, const i
                                  const int32_t *d_c_hat, size_t N, const uint32_t *h_order, const size_t *h_off, size_t G,
                                  int32_t *d_alpha_hat);
 
+/* ---- the key sort of hash_ag for MANY committees on the device (csrc/fz_vk_order.hip; the entries: csrc/fz_vk_order_capi.hip) ----
+ * fz_sort_by_vk_string_ragged on the device, a wave per committee: group g = rows h_off[g] .. h_off[g + 1] - 1 of d_vk
+ * [N][2][degree] (DEVICE memory, any int32 values); h_off [G + 1] and h_valid [N] (optional; NULL: every row) in HOST memory,
+ * copied into pinned staging that the kernel reads in place and consumed when the call returns.  d_order (DEVICE memory, uint32)
+ * receives the GLOBAL row indices: group g's rows with h_valid set, in the order sorted(key=str) puts their keys (code-point
+ * order of str(OneTimeVerificationKey), stable), compacted at goff[g] = the number of valid rows in the groups before it.  With no
+ * mask that is a permutation of each group in place; entries of d_order from goff[G] on are not written.
+ * In this order: FZ_E_BADARG for a NULL context or parameters, a NULL device pointer with N > 0 (h_off with G > 0), parameters that
+ * do not belong to the context, d_vk not 16-byte or d_order not 4-byte aligned, graph capture, N or G of 2^31 or more, offsets that
+ * do not start at 0 or decrease, h_off[G] != N; FZ_E_UNSUPPORTED for a degree that is no power of two from 4 to 256.  Nothing is
+ * enqueued when a code is returned; N == 0 or G == 0 does nothing.  Asynchronous on the context's stream: the kernel alone. */
+FZ_API int fz_sort_by_vk_string_ragged_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, size_t N, const size_t *h_off,
+                                           size_t G, const uint8_t *h_valid, uint32_t *d_order);
+/* fz_hash_ag_ragged_dev with the sort on the device: committee g hashes its rows h_off[g] .. h_off[g + 1] - 1 with h_valid set
+ * (h_valid [h_off[G]] in HOST memory, optional; NULL: every row) in the order above, which is written to scratch of the context's
+ * and read from there by the hash kernel.  The hash kernel's group table -- longest first, committees without a valid signer
+ * dropped -- comes from h_off and h_valid alone.  d_alpha_hat [N][degree] is cleared first and holds, bit for bit, what
+ * fz_hash_ag_ragged_dev writes when it is handed fz_sort_by_vk_string_ragged's order filtered by the mask.  Refusals: those of
+ * fz_hash_ag_ragged_dev in its order (an empty committee and h_off[G] > N included; there is no order list to check).  Nothing is
+ * enqueued when a code is returned.  Asynchronous on the context's stream, no host synchronisation. */
+FZ_API int fz_hash_ag_ragged_sorted_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const uint8_t *d_pre,
+                                        const int32_t *d_c_hat, size_t N, const size_t *h_off, size_t G, const uint8_t *h_valid,
+                                        int32_t *d_alpha_hat);
+/* fz_challenge_hat_msgs_dev with the [N][32] digests left in DEVICE memory (d_prehash_out, 16-byte aligned, required with N > 0),
+ * where fz_hash_ag_ragged*_dev reads them: nothing waits for the digests (up to 4608 signers the call does not synchronise at
+ * all; beyond, once, for the upload of the messages, as fz_challenge_hat_msgs_dev does).  Everything else as that entry. */
+FZ_API int fz_challenge_hat_msgs_keep_dev(fz_ctx *ctx, const fz_scheme_params *P, const int32_t *d_vk, const char *h_msgs,
+                                          const size_t *h_msg_off, size_t N, int32_t *d_c_hat, uint8_t *d_prehash_out);
+/* keys d_vk [N][2][degree] taken apart on the device: d_left [N][degree], d_right [N][degree], for the entries that take the halves
+ * as two arrays (fz_aggregate_target_partial_ragged).  FZ_E_BADARG for a NULL context, a NULL pointer with N > 0 or one that is
+ * not 16-byte aligned; FZ_E_UNSUPPORTED unless the degree is a power of two of at least 4.  Asynchronous, allocation-free. */
+FZ_API int fz_vk_halves_async(fz_ctx *ctx, const int32_t *d_vk, size_t N, int32_t *d_left, int32_t *d_right);
+
 /* ---- reference-exact sampling on the host -----------------------------------------
  * CPython's MT19937 `random` exactly as the reference's samplers drive it (random.seed(int), randrange):
  * the same seed yields the same polynomial as algebra/polynomials.py:436-488.  Seeds are the non-negative integers below
