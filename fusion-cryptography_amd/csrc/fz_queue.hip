@@ -233,7 +233,8 @@ int run_batch(fz_queue *Q, Worker &w, std::vector<Job> &jobs, Batch **out_batch,
 }
 
 // one coalesced batch of aggregate+verify (kind 1) or verify (kind 2) calls: G aggregates, their signers back to back.
-// The flow of BatchScheme._hash_ag_many + aggregate_target_partial_ragged + verify_partials (fusion_hip/scheme.py), in C.
+// The flow of BatchScheme._hash_ag_many (the challenge pass and alpha_hat of the call's _Committees) + aggregate_target_partial_ragged
+// + verify_partials (fusion_hip/scheme.py), in C.
 int run_agg_batch_steps(fz_queue *Q, Worker &w, std::vector<Job> &jobs, int kind, std::vector<int> &verdicts);
 // Every exit of the steps below that reports a failure may leave copies FROM THE CALLERS' ROWS in flight on the worker's stream
 // (they are enqueued first): the stream is drained before the failure is reported, so that a caller who frees or recycles its

@@ -166,7 +166,7 @@ class BatchScheme:
             self.ctx = get_context(params.modulus, params.degree, params.root, params.inv_root, device)
         self.hash_ag = hash_ag           # where the many-committee calls hash their coefficients (_hash_ag_form)
         self.device_hash_ag = True       # ... its device form covers the parameter set (off after its first FZ_E_UNSUPPORTED)
-        self.key_sort = key_sort         # ... and where that form sorts the committees' keys (_keys_stay)
+        self.key_sort = key_sort         # ... and where that form sorts the committees' keys (_Committees.sort_dev)
         self.device_hash = True          # per-signer challenge pipeline on the device (falls back to the host if unsupported)
         self.device_sampler = True       # secret polynomials sampled on the device (the same fallback)
         self.A = np.array([z.values for row in params.public_challenge.matrix for z in row], dtype=np.int32)
@@ -883,59 +883,13 @@ class BatchScheme:
         host = g * _HASH_AG_HOST_COMMITTEE_US + n * perms * _HASH_AG_HOST_US / max(1, min(self.threads, g))
         return "device" if device < host else "host"
 
-    def _many_inputs(self, scope, vk, messages, sizes, want_dev=True):
-        """the challenge pass of a many-committee call in the form its hash_ag takes (_hash_ag_form): -> (dK, dC, c_hat, pre).
-        Device form: vk on the device (dK, an upload into `scope` unless it is there; the challenge pass reads the same copy),
-        c_hat stays there (None for the host copy), the prehashes come back.  Host form: dK None (nothing the call did not
-        upload before), the host copies of c_hat and the prehashes, and dC unless want_dev is False."""
-        if self._hash_ag_form(sizes) == "device":
-            dK = self._take(scope, vk, (int(sum(sizes)), 2, self.d))
-            return (dK,) + self._challenges_keep(scope, dK, messages)
-        if want_dev:
-            return (None,) + self._challenges_both(vk, messages, scope=scope)
-        with DeviceScope() as t:                            # hash_ag reads the host copy; nothing needs c_hat on the device
-            return (None, None) + self._challenges_both(vk, messages, scope=t)[1:]
-
-    def _keys_stay(self, sizes):
-        """does the call over committees of `sizes` sort their keys on the device (key_sort="device" under the device form of
-        hash_ag)?  Then nothing needs a host copy of the keys: L and R are None from here on."""
-        return self.key_sort == "device" and self._hash_ag_form(sizes) == "device"
-
-    def _challenges_keep(self, scope, dK, messages):
-        """the challenge pass in front of hash_ag's device form: -> (dC [N][d] in `scope`, None, the digests [N][32]).  As it was:
-        c_hat stays on the device, the digests come back.  key_sort="device": the digests stay on the device too, a DeviceArray
-        in `scope` (fz_challenge_hat_msgs_keep_dev: nothing is downloaded and nothing waited for); a parameter set the device
-        pipeline does not cover takes the host pipeline as everywhere (_challenges_both)"""
-        if self.key_sort == "device" and self.device_hash:
-            n = len(messages)
-            blob, moff = hostpipe._pack_messages(messages)
-            dC, dP = self._new(scope, (n, self.d)), self._new(scope, (n, 32), np.uint8)
-            try:
-                self.ctx.challenge_msgs_keep_dev(self.P, dK.ptr, blob, moff, n, dC.ptr, dP.ptr)
-                return dC, None, dP
-            except FusionHipError as e:
-                if e.code != FZ_E_UNSUPPORTED:
-                    raise
-                self.device_hash = False
-        return self._challenges_both(dK, messages, want_host=False, scope=scope, want_pre=True)
-
-    def _halves_dev(self, scope, L, R, dK):
-        """the keys' halves as two device arrays [N][d]: uploads of the host copies, or -- the keys stayed on the device
-        (_keys_stay: L is None) -- dK [N][2][d] taken apart there"""
-        if L is not None:
-            return self._up(scope, L), self._up(scope, R)
-        n = dK.shape[0]
-        dL, dR = self._new(scope, (n, self.d)), self._new(scope, (n, self.d))
-        self.ctx.vk_halves_dev(dK.ptr, n, dL.ptr, dR.ptr)
-        return dL, dR
-
     def sort_keys_many_dev(self, vk, sizes, valid=None):
         """the order in which hash_ag hashes the keys of G committees (sizes = keys per committee, concatenated), computed ON THE
         DEVICE (fz_sort_by_vk_string_ragged_dev, a wave per committee): -> int64 row indices into vk [sum N][2][d] (numpy or
         DeviceArray), committee after committee, each committee's rows with valid[i] set (None: all) in the order
         sorted(key=str) puts their keys -- hostpipe.sort_by_vk_string_ragged's order, filtered."""
         sizes = [int(x) for x in sizes]
-        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        off = _offsets(sizes)
         n = int(off[-1])
         if any(x < 0 for x in sizes) or n != self._signer_count(vk):
             raise FusionHipError(FZ_E_BADARG, f"sizes sum to {n} but {self._signer_count(vk)} keys were given")
@@ -947,32 +901,6 @@ class BatchScheme:
             dO = self._new(s, (n,), np.uint32)
             self.ctx.sort_by_vk_string_ragged_dev(self.P, dK.ptr, n, off, valid, dO.ptr)
             return dO.numpy()[:m].astype(np.int64)
-
-    def _alpha_hat_many_dev(self, scope, dK, dC, pre, L, R, off, valid=None):
-        """_alpha_hat_many on the device (fz_hash_ag_ragged_dev, a wave per committee): every group's keys sorted by str(vk) on
-        the host (one C call over all groups; the sort is stable, so the valid signers' order is that order filtered, as in
-        screened_alpha_coefficients), the prehashes uploaded, one call: -> dAl [sum N][d] in `scope`, zero rows for the signers
-        valid[i] leaves out.  dK [sum N][2][d] and dC [sum N][d] are read where they are: c_hat is not downloaded and no
-        coefficient is uploaded.  FusionHipError(FZ_E_UNSUPPORTED) for a parameter set the kernel does not cover.
-        key_sort="device": the sort runs on the device as well (fz_hash_ag_ragged_sorted_dev; L and R are not looked at), and
-        digests that are on the device already (pre a DeviceArray, _challenges_keep) are read where they are."""
-        n = int(off[-1])
-        if self.key_sort == "device":
-            dP = pre if isinstance(pre, DeviceArray) else self._up(scope, np.ascontiguousarray(pre, dtype=np.uint8).reshape(n, 32))
-            dAl = self._new(scope, (n, self.d))
-            self.ctx.hash_ag_ragged_sorted_dev(self.P, dK.ptr, dP.ptr, dC.ptr, n, off, valid, dAl.ptr)
-            return dAl
-        order = hostpipe.sort_by_vk_string_ragged(self.P, L, R, off, self.threads)
-        goff = np.asarray(off, dtype=np.int64)
-        if valid is not None:
-            keep = np.asarray(valid, dtype=bool).reshape(n)[order]
-            counts = np.add.reduceat(keep.astype(np.int64), goff[:-1]) if n else np.zeros(0, dtype=np.int64)
-            order = order[keep]
-            goff = np.concatenate([[0], np.cumsum(counts[counts > 0])]).astype(np.int64)
-        dP = self._up(scope, np.ascontiguousarray(pre, dtype=np.uint8).reshape(n, 32))
-        dAl = self._new(scope, (n, self.d))
-        self.ctx.hash_ag_ragged_dev(self.P, dK.ptr, dP.ptr, dC.ptr, n, order, goff, dAl.ptr)
-        return dAl
 
     def hash_ag_many_dev(self, vk, messages, sizes, valid=None, scope=None):
         """Everything the many-committee calls derive from the keys and messages of G committees (sizes = signers per committee,
@@ -986,60 +914,23 @@ class BatchScheme:
             with DeviceScope() as tmp:
                 dC, dAl, off = self.hash_ag_many_dev(vk, messages, sizes, valid, tmp)
                 return tmp.release(dC), tmp.release(dAl), off
-        sizes = self._many_sizes(vk, messages, sizes)
-        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        dK = self._take(scope, vk, (int(off[-1]), 2, self.d))
-        L = R = None
-        if self.key_sort != "device":
-            _, L, R = self._split_vk(vk)
-        dC, _, pre = self._challenges_keep(scope, dK, messages)
-        return dC, self._alpha_hat_many_dev(scope, dK, dC, pre, L, R, off, valid), off
-
-    def _alpha_hat_many(self, scope, off, L, R, pre, c_hat, valid=None, dK=None, dC=None):
-        """hash_ag's coefficients for the G = len(off) - 1 independent aggregates of rows off[g]:off[g+1], over the signers with
-        valid[i] set (None: all): -> dAl [sum N][d] in `scope`.  THE place where the many-committee calls branch on
-        self.hash_ag.  With dK (what _many_inputs returns for the device form): _alpha_hat_many_dev from dK and dC; its
-        FZ_E_UNSUPPORTED turns the device form off for this object and goes on here with a host copy of c_hat.  Host form: one
-        host thread per aggregate for its sort + serial SHAKE-256 (the sponges are what bounds a
-        lone aggregate: independent aggregates hide each other's), zero rows without hashing for a group with no valid signer,
-        then ONE upload + transform of all rows."""
-        from concurrent.futures import ThreadPoolExecutor
-        if dK is not None:
-            try:
-                return self._alpha_hat_many_dev(scope, dK, dC, pre, L, R, off, valid)
-            except FusionHipError as e:
-                if e.code != FZ_E_UNSUPPORTED:
-                    raise
-                self.device_hash_ag = False
-            if c_hat is None:
-                c_hat = dC.numpy()
-            if L is None:                                   # (the keys and the digests stayed on the device for the form that refused)
-                _, L, R = self._split_vk(dK)
-            if isinstance(pre, DeviceArray):
-                pre = pre.numpy()
-        g = len(off) - 1
-        per = max(1, self.threads // max(1, g))
-
-        def one(k):
-            a, b = off[k], off[k + 1]
-            ok = None if valid is None else valid[a:b]
-            if ok is not None and not ok.any():
-                return np.zeros((b - a, self.d), dtype=np.int32)
-            return screened_alpha_coefficients(self.P, L[a:b], R[a:b], pre[a:b], c_hat[a:b], ok, per)[1]
-        with ThreadPoolExecutor(max_workers=min(g, self.threads)) as pool:      # the C calls release the GIL
-            alpha = np.concatenate(list(pool.map(one, range(g))))
-        return self._alpha_hat(scope, alpha)
+        m = _Committees(self, scope, vk, messages, self._many_sizes(vk, messages, sizes), device_only=True)
+        m.keys_dev()
+        if not m.sort_dev:
+            m.keys_host()
+        m.challenges()
+        return m.dC, m.alpha_hat(valid), m.off
 
     def _hash_ag_many(self, scope, vk, messages, sizes):
         """hash_ag for G independent aggregates whose signers are concatenated (aggregate g = rows off[g]:off[g+1]; sizes as
-        _many_sizes passed them): ONE device pass for all challenges, _alpha_hat_many.  -> (dC, dAl [sum N][d], offsets, L, R,
-        dK), the buffers in `scope`; L and R are None where the keys stay on the device (_keys_stay: _halves_dev takes dK)"""
-        L = R = None
-        if not self._keys_stay(sizes):
-            vk, L, R = self._split_vk(vk)
-        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        dK, dC, c_hat, pre = self._many_inputs(scope, vk, messages, sizes)
-        return dC, self._alpha_hat_many(scope, off, L, R, pre, c_hat, dK=dK, dC=dC), off, L, R, dK
+        _many_sizes passed them): ONE device pass for all challenges, then _Committees.alpha_hat: -> (the call's _Committees, with
+        c_hat on the device (dC); dAl [sum N][d]), the buffers in `scope`.  Unless the sort runs on the device the challenge pass
+        reads the host copy of the keys, which is made first."""
+        m = _Committees(self, scope, vk, messages, sizes)
+        if not m.sort_dev:
+            m.keys_host(adopt=True)
+        m.challenges()
+        return m, m.alpha_hat()
 
     def aggregate_many(self, vk, messages, sig, sizes):
         """G independent aggregate() calls (fusion.py:655; the reference is called once per aggregate) as one batch:
@@ -1048,11 +939,10 @@ class BatchScheme:
         aggregate(params, keys_g, messages_g, signatures_g).signature_hat.  One launch for all aggregates."""
         sizes = self._many_sizes(vk, messages, sizes)
         with DeviceScope() as s:
-            dC, dAl, off, _, _, _ = self._hash_ag_many(s, vk, messages, sizes)
-            g = len(off) - 1
-            dS = self._take(s, sig, (int(off[-1]), self.l, self.d))
-            dO = self._new(s, (g, self.l, self.d))
-            self.ctx.aggregate_core_ragged_dev(dS.ptr, dAl.ptr, off, self.l, dO.ptr)
+            m, dAl = self._hash_ag_many(s, vk, messages, sizes)
+            dS = self._take(s, sig, (m.n, self.l, self.d))
+            dO = self._new(s, (m.g, self.l, self.d))
+            self.ctx.aggregate_core_ragged_dev(dS.ptr, dAl.ptr, m.off, self.l, dO.ptr)
             return dO.numpy()
 
     def verify_many(self, vk, messages, aggregates, sizes):
@@ -1065,15 +955,58 @@ class BatchScheme:
             return out
         sizes = self._many_sizes(vk, messages, sizes)
         with DeviceScope() as s:
-            dC, dAl, off, L, R, dK = self._hash_ag_many(s, vk, messages, sizes)
-            dL, dR = self._halves_dev(s, L, R, dK)
+            m, dAl = self._hash_ag_many(s, vk, messages, sizes)
+            dL, dR = m.halves_dev()
             dS = self._take(s, aggregates, (g, self.l, self.d))
-            dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, dC, dAl, off)
+            dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, m.dC, dAl, m.off)
             self.ctx.verify_with_target_batch_async_dev(self._A_dev().ptr, dS.ptr, dT.ptr, g, self.l, int(self.params.beta_vf),
                                                         int(self.params.omega_vf), dV.ptr)
             return [_verdict(c) for c in dV.numpy()]
 
     # ---- many aggregates at once, straight from the bytes (not in the reference) ---------
+    def _aggregate_groups(self, vk, messages, data, sizes, screened, encoded, verify):
+        """aggregate_many_encoded, and with `verify` aggregate_verify_many_encoded: ONE body, so that each step is written once and
+        the order of the steps -- what the stream sees -- can be read off it.  The records up, their status words, the check
+        over all records, the challenge pass, the host copy of the keys unless the sort runs on the device, the download of the
+        codes, hash_ag over the records with code 0, the fused launch, the result.  The check is the range check, or with
+        `screened` the keyed verification, which reads the keys and c_hat on the device and so comes behind the challenge pass.
+        Where a launch reads them there (`screened`, `verify`) the keys go to the device first and c_hat stays there; else
+        nothing needs c_hat on the device, and the pass comes behind the keys' host copy."""
+        nrows, bound, rb, data, n, sizes = self._signature_groups(vk, messages, data, sizes)
+        g, keyed = len(sizes), screened or verify
+        if g == 0:
+            return self._aggregates_out(None, None, 0, encoded, np.zeros(0, dtype=np.int32)) + (([],) if verify else ())
+        with DeviceScope() as s:
+            m = _Committees(self, s, vk, messages, sizes)
+            dB, dV = self._records_dev(s, data, n, rb), self._new(s, (n,))
+            if not screened:
+                self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)       # beside the challenge pass
+            if keyed:
+                dK = m.keys_dev()
+                m.challenges()
+            if screened:
+                self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, m.dC.ptr, dV.ptr)
+            if not m.sort_dev:
+                m.keys_host()
+            if not keyed:
+                m.challenges(keep=False)
+            codes = dV.numpy()
+            dAl = m.alpha_hat(codes == 0)
+            dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
+            if not verify:
+                self.ctx.aggregate_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, m.off, self.l, bound, dP.ptr, self.l * self.d, dO.ptr)
+                return self._aggregates_out(s, dO, g, encoded, codes)
+            dT, dW = self._new(s, (g, self.d), np.int64), self._new(s, (g,))
+            self.ctx.aggregate_target_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, dK.ptr, m.dC.ptr, m.off, self.l, bound, dP.ptr,
+                                                               self.l * self.d, dT.ptr, self.d, dO.ptr)
+            self.ctx.verify_partials_batch_async_dev(self._A_dev().ptr, dP.ptr, self.l * self.d, dT.ptr, self.d, g, self.l,
+                                                     int(self.params.beta_vf), int(self.params.omega_vf), dW.ptr)
+            out = self._aggregates_out(s, dO, g, encoded, codes)
+            accepted = np.add.reduceat((codes == 0).astype(np.int64), m.off[:-1])
+            verdicts = [None if a == 0 else (False, VERDICT_REASONS[1]) if a > self.params.capacity else _verdict(c)
+                        for a, c in zip(accepted, dW.numpy())]
+            return out + (verdicts,)
+
     def aggregate_many_encoded(self, vk, messages, data, sizes, screened=False, encoded=False):
         """G independent aggregate_encoded calls (screened=True: aggregate_encoded_screened calls) as one batch: vk [sum N][2][d]
         (numpy or DeviceArray), messages and `data` (sum N "signature" records in every form decode takes) hold the signers of
@@ -1089,33 +1022,7 @@ class BatchScheme:
         one download.  Sizes that do not sum to the numbers of records, keys and messages, a size below 1, or a length that is
         not whole records raise FusionHipError(FZ_E_BADARG) before the device is touched; no records and sizes == [] return
         empty arrays without a device."""
-        nrows, bound, rb, data, n, sizes = self._signature_groups(vk, messages, data, sizes)
-        g = len(sizes)
-        if g == 0:
-            out, extras = self._aggregates_out(None, None, 0, encoded)
-            return (out, np.zeros(0, dtype=np.int32)) + extras
-        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        with DeviceScope() as s:
-            dB = self._records_dev(s, data, n, rb)
-            dV = self._new(s, (n,))
-            dH = dC = None                                  # the keys and c_hat on the device, as hash_ag's device form reads them
-            if screened:
-                dK = self._take(s, vk, (n, 2, self.d))
-                dH, dC, c_hat, pre = self._many_inputs(s, dK, messages, sizes)
-                self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, n, self.l, bound, 0, dK.ptr, dC.ptr, dV.ptr)
-            else:
-                self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
-            L = R = None
-            if not self._keys_stay(sizes):
-                _, L, R = self._split_vk(vk)
-            if not screened:
-                dH, dC, c_hat, pre = self._many_inputs(s, vk, messages, sizes, want_dev=False)
-            codes = dV.numpy()
-            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, codes == 0, dK=dH, dC=dC)
-            dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
-            self.ctx.aggregate_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, off, self.l, bound, dP.ptr, self.l * self.d, dO.ptr)
-            out, extras = self._aggregates_out(s, dO, g, encoded)
-            return (out, codes) + extras
+        return self._aggregate_groups(vk, messages, data, sizes, screened, encoded, False)
 
     def _signature_groups(self, vk, messages, data, sizes):
         """the input of the calls that take groups of "signature" records, refused with FusionHipError(FZ_E_BADARG) unless it is
@@ -1129,19 +1036,20 @@ class BatchScheme:
             raise FusionHipError(FZ_E_BADARG, f"sizes sum to {sum(sizes)} but {n} records were given")
         return nrows, bound, rb, data, n, sizes
 
-    def _aggregates_out(self, s, dO, g, encoded):
-        """how the many-committee calls from the bytes hand back the g aggregates dO [g][l][d] holds on the device: -> (rows
-        [g][l][d] int32, ()), or with encoded (records uint8 [g][encoded_size(params, "aggregate")], (aggregate_codes int32 [g],))
-        -- the aggregates are then never downloaded as rows; g == 0: the empty arrays, no device"""
+    def _aggregates_out(self, s, dO, g, encoded, codes):
+        """how the many-committee calls from the bytes hand back the g aggregates dO [g][l][d] holds on the device, in front of
+        the records' `codes`: -> (rows [g][l][d] int32, codes), or with encoded (records uint8 [g][encoded_size(params,
+        "aggregate")], codes, aggregate_codes int32 [g]) -- the aggregates are then never downloaded as rows; g == 0: the empty
+        arrays, no device"""
         _, _, abound, _, arb = _encoding(self.params, "aggregate")
         if g == 0:
-            return (np.zeros((0, arb), dtype=np.uint8), (np.zeros(0, dtype=np.int32),)) if encoded else \
-                (np.zeros((0, self.l, self.d), dtype=np.int32), ())
+            return (np.zeros((0, arb), dtype=np.uint8), codes, np.zeros(0, dtype=np.int32)) if encoded else \
+                (np.zeros((0, self.l, self.d), dtype=np.int32), codes)
         if not encoded:
-            return dO.numpy(), ()
+            return dO.numpy(), codes
         dR, dW = self._new(s, (g, arb), np.uint8), self._new(s, (g,))
         self.ctx.encode_records_async_dev(dO.ptr, g, self.l, True, abound, dR.ptr, dW.ptr)
-        return dR.numpy(), (dW.numpy(),)
+        return dR.numpy(), codes, dW.numpy()
 
     # ---- aggregate and verify in one pass, straight from the bytes (not in the reference; INTEGRATION.md section G) ---------
     def aggregate_verify_many_encoded(self, vk, messages, data, sizes, encoded=False):
@@ -1159,35 +1067,7 @@ class BatchScheme:
         (fz_aggregate_target_encoded_ragged_async), one for all verdicts straight from the sums
         (fz_verify_partials_batch_async), one download.  Refusals are aggregate_many_encoded's, raised before the device is
         touched; no records and sizes == [] return empty arrays and [] without a device."""
-        nrows, bound, rb, data, n, sizes = self._signature_groups(vk, messages, data, sizes)
-        g = len(sizes)
-        if g == 0:
-            out, extras = self._aggregates_out(None, None, 0, encoded)
-            return (out, np.zeros(0, dtype=np.int32)) + extras + ([],)
-        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        with DeviceScope() as s:
-            dB = self._records_dev(s, data, n, rb)
-            dV = self._new(s, (n,))
-            self.ctx.check_records_async_dev(dB.ptr, n, nrows, bound, dV.ptr)
-            dK = self._take(s, vk, (n, 2, self.d))
-            dH, dC, c_hat, pre = self._many_inputs(s, dK, messages, sizes)     # beside the check
-            L = R = None
-            if dH is None or self.key_sort != "device":
-                _, L, R = self._split_vk(vk)
-            codes = dV.numpy()
-            valid = codes == 0
-            dAl = self._alpha_hat_many(s, off, L, R, pre, c_hat, valid, dK=dH, dC=dC)
-            dP, dO = self._new(s, (g, self.l, self.d), np.int64), self._new(s, (g, self.l, self.d))
-            dT, dW = self._new(s, (g, self.d), np.int64), self._new(s, (g,))
-            self.ctx.aggregate_target_encoded_ragged_async_dev(dB.ptr, dAl.ptr, dV.ptr, dK.ptr, dC.ptr, off, self.l, bound, dP.ptr,
-                                                               self.l * self.d, dT.ptr, self.d, dO.ptr)
-            self.ctx.verify_partials_batch_async_dev(self._A_dev().ptr, dP.ptr, self.l * self.d, dT.ptr, self.d, g, self.l,
-                                                     int(self.params.beta_vf), int(self.params.omega_vf), dW.ptr)
-            out, extras = self._aggregates_out(s, dO, g, encoded)
-            accepted = np.add.reduceat(valid.astype(np.int64), off[:-1])
-            verdicts = [None if a == 0 else (False, VERDICT_REASONS[1]) if a > self.params.capacity else _verdict(c)
-                        for a, c in zip(accepted, dW.numpy())]
-            return (out, codes) + extras + (verdicts,)
+        return self._aggregate_groups(vk, messages, data, sizes, False, encoded, True)
 
     def aggregate_verify_encoded(self, vk, messages, data):
         """aggregate_encoded followed by verify() of the result on the accepted signers, in one pass (the many-committee form
@@ -1223,12 +1103,159 @@ class BatchScheme:
         if out is not None:
             return out
         with DeviceScope() as s:
-            dC, dAl, off, L, R, dK = self._hash_ag_many(s, vk, messages, sizes)
-            dL, dR = self._halves_dev(s, L, R, dK)
+            m, dAl = self._hash_ag_many(s, vk, messages, sizes)
+            dL, dR = m.halves_dev()
             dB = self._records_dev(s, data, g, rb)
-            dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, dC, dAl, off)
+            dV, dT = self._new(s, (g,)), self._targets(s, dL, dR, m.dC, dAl, m.off)
             self.ctx.verify_encoded_async_dev(self._A_dev().ptr, dB.ptr, g, self.l, bound, dT.ptr, 0, 0, dV.ptr)
             return [_verdict(c) for c in dV.numpy()]
+
+
+def _offsets(sizes):
+    """committee sizes -> the int64 offsets [G + 1] of the committees' first rows, and the end"""
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def _order_of_valid(order, off, valid):
+    """a host order of all rows, committee after committee (offsets `off`), filtered by valid [N] (None: all): -> (the valid rows
+    in that order, the offsets of the committees that keep a row).  The sort is stable, so this is the order of the valid rows
+    sorted alone, as in screened_alpha_coefficients."""
+    if valid is None:
+        return order, off
+    keep = np.asarray(valid, dtype=bool).reshape(len(order))[order]
+    counts = np.add.reduceat(keep.astype(np.int64), off[:-1]) if len(order) else np.zeros(0, dtype=np.int64)
+    return order[keep], _offsets(counts[counts > 0])
+
+
+class _Committees:
+    """The inputs of ONE many-committee call of BatchScheme `bs`: the keys `vk` [sum N][2][d] (numpy or DeviceArray) and messages of
+    G committees of `sizes` signers each, concatenated.  Built once per call, inside the call's DeviceScope, touching no device.
+    It owns
+      off, n, g   the offsets [G + 1], made once; sum N; G
+      form        "host" or "device": where hash_ag runs, decided HERE, once, by bs._hash_ag_form (device_only: the device form
+                  whatever that says, and no fall-back from it -- hash_ag_many_dev's contract)
+      sort_dev    does the device form sort the keys on the device?  THE predicate for "no host copy of the keys is needed":
+                  then the digests stay on the device as well
+      vk, keys    the keys as they came, and what the challenge pass and an upload of the keys read: vk, its host copy where
+                  keys_host(adopt=True) made it, dK once that exists
+    and what the call derives, each made at most once by the method that says where it lives (the attributes are None before):
+      keys        keys_dev() -> dK [N][2][d] on the device; keys_host() -> (L, R) [N][d] on the host; halves_dev() -> the halves
+                  on the device, uploads of L and R or -- sort_dev -- dK taken apart there
+      challenges  challenges() runs the pass and leaves c_hat on the device (dC), on the host (c_hat) or both, and the digests
+                  on the host (pre) or -- sort_dev -- on the device (dP [N][32]), as the form needs them
+      the rest    host_copies() -> (c_hat, L, R, pre), downloads of what is on the device only; alpha_hat() uploads the digests
+                  where hash_ag's device form finds them on the host
+    alpha_hat() is the one place that chooses between the forms of hash_ag.  Nothing here moves a transfer: a method called a
+    second time returns what the first call made, and the CALLER's order of first calls is the order the stream sees.  Device
+    buffers are the scope's (or the caller's own DeviceArray), never this object's."""
+
+    def __init__(self, bs, scope, vk, messages, sizes, device_only=False):
+        self.bs, self.scope, self.vk, self.keys, self.messages, self.device_only = bs, scope, vk, vk, messages, device_only
+        self.off = _offsets(sizes)
+        self.n, self.g = int(self.off[-1]), len(sizes)
+        form = bs._hash_ag_form(sizes)                      # every call asks once, here; device_only overrules the answer
+        self.form = "device" if device_only else form
+        self.sort_dev = self.form == "device" and bs.key_sort == "device"
+        self.dK = self.dC = self.dP = self.L = self.R = self.c_hat = self.pre = None
+
+    def keys_dev(self):
+        if self.dK is None:
+            self.dK = self.keys = self.bs._take(self.scope, self.keys, (self.n, 2, self.bs.d))
+        return self.dK
+
+    def keys_host(self, adopt=False):
+        """(L, R); adopt: the challenge pass and keys_dev() read this copy from here on (an upload, where vk came as a DeviceArray).
+        sort_dev, so only after the device form refused: the copy of the keys that form read is the one downloaded"""
+        if self.L is None:
+            vk, self.L, self.R = self.bs._split_vk(self.dK if self.sort_dev else self.vk)
+            if adopt:
+                self.keys = vk
+        return self.L, self.R
+
+    def halves_dev(self):
+        bs, s = self.bs, self.scope
+        if not self.sort_dev:
+            return tuple(bs._up(s, half) for half in self.keys_host())
+        dL, dR = bs._new(s, (self.n, bs.d)), bs._new(s, (self.n, bs.d))
+        bs.ctx.vk_halves_dev(self.keys_dev().ptr, self.n, dL.ptr, dR.ptr)
+        return dL, dR
+
+    def host_copies(self):
+        """-> (c_hat, L, R, pre) on the host: each a download of the device's copy unless it is there"""
+        if self.c_hat is None:
+            self.c_hat = self.dC.numpy()
+        L, R = self.keys_host()
+        if self.pre is None:
+            self.pre = self.dP.numpy()
+        return self.c_hat, L, R, self.pre
+
+    def challenges(self, keep=True):
+        """the challenge pass in the way of the form.  Host form: c_hat and the digests on the host, and c_hat on the device unless
+        keep is False (hash_ag reads the host copy; nothing then needs it there).  Device form: from dK, c_hat stays on the device
+        and the digests come back -- or, sort_dev, stay there as well (fz_challenge_hat_msgs_keep_dev: nothing is downloaded and
+        nothing waited for).  A parameter set the device pipeline does not cover takes the host pipeline as everywhere
+        (BatchScheme._challenges_both), which leaves host copies in every form."""
+        bs, s = self.bs, self.scope
+        if self.form == "device":
+            dK = self.keys_dev()
+            if self.sort_dev and bs.device_hash:
+                blob, moff = hostpipe._pack_messages(self.messages)
+                dC, dP = bs._new(s, (self.n, bs.d)), bs._new(s, (self.n, 32), np.uint8)
+                try:
+                    bs.ctx.challenge_msgs_keep_dev(bs.P, dK.ptr, blob, moff, self.n, dC.ptr, dP.ptr)
+                    self.dC, self.dP = dC, dP
+                    return
+                except FusionHipError as e:
+                    if e.code != FZ_E_UNSUPPORTED:
+                        raise
+                    bs.device_hash = False
+            self.dC, self.c_hat, self.pre = bs._challenges_both(dK, self.messages, want_host=False, scope=s, want_pre=True)
+        else:
+            with DeviceScope() as t:                        # keep=False: c_hat leaves the device once its host copy is here
+                dC, self.c_hat, self.pre = bs._challenges_both(self.keys, self.messages, scope=s if keep else t)
+            self.dC = dC if keep else None
+
+    def alpha_hat(self, valid=None):
+        """hash_ag's coefficients for the G committees, over the signers with valid[i] set (None: all): -> dAl [sum N][d] in the
+        scope, zero rows for the others.  THE place where the many-committee calls branch on the form.
+        Device form: a wave per committee, from dK and dC where they are -- c_hat is not downloaded and no coefficient uploaded --,
+        the keys sorted by str(vk) on the host (one C call over all committees; fz_hash_ag_ragged_dev takes the order) or, sort_dev,
+        on the device as well (fz_hash_ag_ragged_sorted_dev), the digests uploaded unless they are there.  FZ_E_UNSUPPORTED, for a
+        parameter set the kernel does not cover, turns the device form off for the BatchScheme, which stays there, and this call
+        goes on with the host form on host_copies().
+        Host form: one host thread per committee for its sort + serial SHAKE-256 (the sponges are what bounds a lone aggregate:
+        independent aggregates hide each other's), zero rows without hashing for a committee with no valid signer, then ONE
+        upload + transform of all rows."""
+        bs, off, g, n = self.bs, self.off, self.g, self.n
+        if self.form == "device":
+            try:
+                if self.sort_dev:
+                    entry, rows = bs.ctx.hash_ag_ragged_sorted_dev, (off, valid)
+                else:
+                    order = hostpipe.sort_by_vk_string_ragged(bs.P, *self.keys_host(), off, bs.threads)
+                    entry, rows = bs.ctx.hash_ag_ragged_dev, _order_of_valid(order, off, valid)
+                if self.dP is None:
+                    self.dP = bs._up(self.scope, np.ascontiguousarray(self.pre, dtype=np.uint8).reshape(n, 32))
+                dAl = bs._new(self.scope, (n, bs.d))
+                entry(bs.P, self.dK.ptr, self.dP.ptr, self.dC.ptr, n, *rows, dAl.ptr)
+                return dAl
+            except FusionHipError as e:
+                if e.code != FZ_E_UNSUPPORTED or self.device_only:
+                    raise
+                bs.device_hash_ag = False
+        from concurrent.futures import ThreadPoolExecutor
+        c_hat, L, R, pre = self.host_copies()
+        per = max(1, bs.threads // max(1, g))
+
+        def one(k):
+            a, b = off[k], off[k + 1]
+            ok = None if valid is None else valid[a:b]
+            if ok is not None and not ok.any():
+                return np.zeros((b - a, bs.d), dtype=np.int32)
+            return screened_alpha_coefficients(bs.P, L[a:b], R[a:b], pre[a:b], c_hat[a:b], ok, per)[1]
+        with ThreadPoolExecutor(max_workers=min(g, bs.threads)) as pool:      # the C calls release the GIL
+            alpha = np.concatenate(list(pool.map(one, range(g))))
+        return bs._alpha_hat(self.scope, alpha)
 
 
 def _verdict(code):

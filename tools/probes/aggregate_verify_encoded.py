@@ -108,7 +108,7 @@ def kernel(bs, secpar, shape):
 
 def e2e(bs, secpar, shape):
     from fusion_hip.context import DeviceScope
-    from fusion_hip.scheme import _encoding
+    from fusion_hip.scheme import _Committees, _encoding
     l, d = bs.l, bs.d
     rows, coef, bound, w, rb = _encoding(bs.params, "signature")
     sizes = sizes_of(shape)
@@ -143,12 +143,12 @@ def e2e(bs, secpar, shape):
     # what the second call repeats: one challenge pass over all signers, one hash_ag per committee (on aggregate_many's pool)
     def repeated():
         with DeviceScope() as s:
+            m = _Committees(bs, s, vk, msgs, sizes)           # (hash_ag="host": the host form)
             t0 = time.perf_counter()
-            dC, c_hat, pre = bs._challenges_both(vk, msgs, scope=s)
+            m.challenges()
             t1 = time.perf_counter()
-            _, L, R = bs._split_vk(vk)
-            off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            bs._alpha_hat_many(s, off, L, R, pre, c_hat)
+            m.keys_host()
+            m.alpha_hat()
             bs.ctx.synchronize()
             return t1 - t0, time.perf_counter() - t1
     t_old = t_new = t_ch = t_ag = 1e30

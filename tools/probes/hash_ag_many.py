@@ -1,11 +1,11 @@
 """hash_ag for many committees: the device form (fz_hash_ag_ragged_dev, a wave per committee) against the host form
-(BatchScheme._alpha_hat_many on the scheme's thread pool), on the same box and in the same process.
+(the host form of fusion_hip.scheme._Committees.alpha_hat, on the scheme's thread pool), on the same box and in the same process.
 
 Per cell G x n (G committees of n signers) and parameter set:
   step   the hash_ag step alone, from what the challenge pass leaves (keys, pre-hashes, c_hat) to alpha_hat on the device:
            entry   fz_hash_ag_ragged_dev by device events (memset, kernel, transform), order list given
-           device  BatchScheme._alpha_hat_many_dev, wall clock to a synchronise: the ragged key sort, the upload of the pre-hashes, the entry
-           host    BatchScheme._alpha_hat_many under hash_ag="host" with threads=THREADS, wall clock to a synchronise (the c_hat
+           device  _Committees.alpha_hat in its device form, wall clock to a synchronise: the ragged key sort, the upload of the pre-hashes, the entry
+           host    _Committees.alpha_hat under hash_ag="host" with threads=THREADS, wall clock to a synchronise (the c_hat
                    download before it is not counted; the upload and transform of the coefficients are: they are its own)
          on synthetic centred rows (the entry takes any), a fresh window of a larger pool for every repetition; medians of REPS
          repetitions, the forms alternating; spread = (max - min) / median.
@@ -74,6 +74,7 @@ def pool(bs, n, windows):
 def step_cell(bs, sizes, reps=REPS, forms=("entry", "device", "host")):
     from fusion_hip.context import DeviceScope
     from fusion_hip import hostpipe
+    from fusion_hip.scheme import _Committees
     ctx = bs.ctx
     n = sum(sizes)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -94,11 +95,12 @@ def step_cell(bs, sizes, reps=REPS, forms=("entry", "device", "host")):
                     ms = ctx.timer_stop_ms()
                     a_dev = dAl
                 else:
+                    # the call's inputs as the challenge pass leaves them; bs has hash_ag="host": device_only picks the device form
+                    m = _Committees(bs, s, vk, None, sizes, device_only=f == "device")
+                    m.dK, m.dC, m.L, m.R, m.pre, m.c_hat = dK, dC, L, R, pre, c
                     t0 = time.perf_counter()
-                    if f == "device":
-                        a = bs._alpha_hat_many_dev(s, dK, dC, pre, L, R, off)
-                    else:
-                        a = bs._alpha_hat_many(s, off, L, R, pre, c)
+                    a = m.alpha_hat()
+                    if f == "host":
                         a_host = a
                     ctx.synchronize()
                     ms = (time.perf_counter() - t0) * 1e3

@@ -5,7 +5,7 @@ copy of the keys, the digests downloaded and uploaded again), on the same box an
 The cells and the method are tools/probes/hash_ag_many.py's: G committees of n signers, both parameter sets, medians of REPS
 repetitions on fresh inputs, the forms alternating; spread = (max - min) / median.
   step   the hash_ag step alone, from what the challenge pass leaves to alpha_hat on the device, wall clock to a synchronise:
-           host sort      BatchScheme._alpha_hat_many_dev under key_sort="host": the ragged sort of host-resident keys, the upload
+           host sort      fusion_hip.scheme._Committees.alpha_hat under key_sort="host": the ragged sort of host-resident keys, the upload
                           of the digests, the entry
            + key download the same when the keys live on the device: the download of [N][2][d] in front of it
            device sort    ... under key_sort="device": the entry alone (keys and digests are where the challenge pass left them)
@@ -54,6 +54,7 @@ def pool(bs, n, windows):
 
 def step_cell(host, dev, sizes):
     from fusion_hip.context import DeviceScope
+    from fusion_hip.scheme import _Committees
     ctx = host.ctx
     n = sum(sizes)
     off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -74,14 +75,18 @@ def step_cell(host, dev, sizes):
                     ctx.hash_ag_ragged_sorted_dev(dev.P, dK.ptr, dP.ptr, dC.ptr, n, off, None, dAl.ptr)
                     ms = ctx.timer_stop_ms()
                 else:
-                    t0 = time.perf_counter()
+                    # the call's inputs as its challenge pass leaves them: the digests on the device under the device sort, else on
+                    # the host beside a host copy of the keys -- which "+ key download" leaves alpha_hat to fetch from the device
+                    m = _Committees(dev if f == "device sort" else host, s, dK, None, sizes)
+                    m.dK, m.dC = dK, dC
                     if f == "device sort":
-                        dAl = dev._alpha_hat_many_dev(s, dK, dC, dP, None, None, off)
-                    elif f == "host sort":
-                        dAl = host._alpha_hat_many_dev(s, dK, dC, pre, L, R, off)
+                        m.dP = dP
                     else:
-                        _, l2, r2 = host._split_vk(dK)
-                        dAl = host._alpha_hat_many_dev(s, dK, dC, pre, l2, r2, off)
+                        m.pre = pre
+                    if f == "host sort":
+                        m.L, m.R = L, R
+                    t0 = time.perf_counter()
+                    dAl = m.alpha_hat()
                     ctx.synchronize()
                     ms = (time.perf_counter() - t0) * 1e3
                 outs[f] = dAl
