@@ -11,8 +11,17 @@ model entry records its arguments and the calling thread, can block on a gate an
 driver, not of the product.  Every expected value is the model applied to that call's inputs alone; comparisons are exact.
 
 The program runs with FZ_POOL_MB=0 (every fz_free is a hipFree: AddressSanitizer sees a read of a block that went back too
-early) in two builds: address + undefined behaviour with leak detection, and ThreadSanitizer.  Scenarios S1 .. S10 are listed
-at their functions."""
+early) in three builds: address + undefined behaviour with leak detection, ThreadSanitizer, and no sanitizer.  Scenarios
+S1 .. S11 are listed at their functions.
+
+With "trace" as its argument the program prints, instead, the trace of fixed one-worker flows, one line per event: every call of
+the stub runtime (function, bytes -- for a free, the bytes of its block --, copy kind, the caller's or the worker's thread, the
+worker's stream, a consumer's or none), every model entry (entry, N, G, offsets, sig_null), every refusal of S8 and every batch
+failure with its code and its whole error text; no addresses, no tickets.  tests/golden/queue_runtime_trace.txt is that output
+of the unit as it was BEFORE its steps were written once (docs/HISTORY.md AH); all three builds must print exactly it, so a
+runtime call, allocation or copy that moved, changed thread or changed stream shows as a differing line.  The one path the trace
+cannot reach is fz_queue_release_after waiting on its event itself: it needs std::vector::push_back to throw under the queue's
+mutex, and the stub's controls fail device allocations and event creations only."""
 import os
 import subprocess
 
@@ -26,6 +35,7 @@ DRIVER = STUB + r'''
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <map>
 #include <memory>
 #include <thread>
 
@@ -155,6 +165,43 @@ static void arm(int entry, long skip, int code, const std::string &msg) {       
 static void disarm() { std::lock_guard<std::mutex> g(m_mu); for (long &f : m_fail_at) f = -1; }
 static std::vector<MRec> model_log(size_t mark = 0) { std::lock_guard<std::mutex> g(m_mu); return std::vector<MRec>(m_log.begin() + (long)mark, m_log.end()); }
 static size_t model_mark() { std::lock_guard<std::mutex> g(m_mu); return m_log.size(); }
+
+// ---- the trace mode ("trace" as the program's argument): what the flows at the end of this file print -------------------
+static bool g_trace = false, g_quiet = false;           // g_quiet: this part of a trace run is checked, not printed
+static int g_caller_tid = -1;                            // main's; every other thread that logs in a one-worker flow is the worker
+static std::set<const void *> g_consumer_streams;
+static size_t g_stub_mark = 0, g_model_mark = 0;
+static const char *const ENTRY[E_COUNT] = {"sample", "keygen", "challenge", "sign", "ntt", "ragged", "verify_partials", "verify_target", "reduce"};
+static int R(int rc) { if (g_trace && !g_quiet && rc != FZ_OK) printf("refusal code=%d text=%s\n", rc, fz_last_error()); return rc; }
+static int F(const char *where, int rc) { if (g_trace && !g_quiet && rc != FZ_OK) printf("failure %s code=%d text=%s\n", where, rc, fz_last_error()); return rc; }
+// both logs since the last dump, merged by sequence number: no addresses, no tickets
+static void tdump(bool print = true) {
+    if (!g_trace) return;
+    print = print && !g_quiet;
+    const std::vector<Call> s = stub_log(g_stub_mark);
+    const std::vector<MRec> m = model_log(g_model_mark);
+    g_stub_mark += s.size();
+    g_model_mark += m.size();
+    static std::map<const void *, size_t> bytes;         // a free prints the size of its block: which block went, without its address
+    static const char *const KIND[5] = {"h2h", "h2d", "d2h", "d2d", "default"};
+    for (size_t i = 0, j = 0; i < s.size() || j < m.size();) {
+        if (j == m.size() || (i < s.size() && s[i].seq < m[j].seq)) {
+            const Call &r = s[i++];
+            if (r.fn == "hipMalloc" || r.fn == "hipHostMalloc") bytes[r.p] = r.n;
+            const size_t n = r.fn == "hipFree" || r.fn == "hipHostFree" ? bytes[r.p] : r.n;
+            if (!print) continue;
+            printf("hip %s n=%zu kind=%s thread=%s stream=%s\n", r.fn.c_str(), n, r.kind < 0 || r.kind > 4 ? "-" : KIND[r.kind],
+                   r.tid == g_caller_tid ? "caller" : "worker", !r.stream ? "none" : g_consumer_streams.count(r.stream) ? "consumer" : "worker");
+        } else {
+            const MRec &r = m[j++];
+            if (!print) continue;
+            printf("model %s N=%zu G=%zu offs=[", ENTRY[r.entry], r.N, r.G);
+            for (size_t k = 0; k < r.offs.size(); ++k) printf(k ? ",%zu" : "%zu", r.offs[k]);
+            printf("] sig_null=%d thread=%s\n", (int)r.sig_null, r.tid == g_caller_tid ? "caller" : "worker");
+        }
+    }
+    fflush(stdout);
+}
 
 extern "C" {
 int fz_sample_secret_polys_dev(fz_ctx *, const uint64_t *h_seeds, size_t N, int64_t modulus, int degree, int64_t norm_bound, int64_t weight_bound, int32_t *d_out) {
@@ -707,20 +754,20 @@ static void s7_destroy() {
 static void s8_refusals() {
     fz_queue *Q = nullptr;
     fz_scheme_params bad = g_P;
-    CHECK(fz_queue_create(0, nullptr, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q) == FZ_E_BADARG);
-    CHECK(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, nullptr, 1, 8, &Q) == FZ_E_BADARG);
-    CHECK(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, nullptr) == FZ_E_BADARG);
+    CHECK(R(fz_queue_create(0, nullptr, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q)) == FZ_E_BADARG);
+    CHECK(R(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, nullptr, 1, 8, &Q)) == FZ_E_BADARG);
+    CHECK(R(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, nullptr)) == FZ_E_BADARG);
     Q = (fz_queue *)&bad;
-    CHECK(fz_queue_create(0, &g_P, 0, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q) == FZ_E_BADARG && !Q);
-    for (int w : {0, 17}) CHECK(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), w, 8, &Q) == FZ_E_BADARG && !Q);
-    CHECK(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 0, &Q) == FZ_E_BADARG && !Q);
+    CHECK(R(fz_queue_create(0, &g_P, 0, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q)) == FZ_E_BADARG && !Q);
+    for (int w : {0, 17}) CHECK(R(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), w, 8, &Q)) == FZ_E_BADARG && !Q);
+    CHECK(R(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 0, &Q)) == FZ_E_BADARG && !Q);
     bad.modulus = 0;
-    CHECK(fz_queue_create(0, &bad, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q) == FZ_E_BADARG && !Q);
+    CHECK(R(fz_queue_create(0, &bad, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q)) == FZ_E_BADARG && !Q);
     bad.modulus = 1ll << 32;
-    CHECK(fz_queue_create(0, &bad, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q) == FZ_E_BADARG && !Q);
+    CHECK(R(fz_queue_create(0, &bad, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q)) == FZ_E_BADARG && !Q);
     bad = g_P;
     bad.degree = 0;
-    CHECK(fz_queue_create(0, &bad, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q) == FZ_E_BADARG && !Q);
+    CHECK(R(fz_queue_create(0, &bad, RANK, BETA_SK, OMEGA_SK, g_A.data(), 1, 8, &Q)) == FZ_E_BADARG && !Q);
 
     Q = mkq(1, (size_t)1 << 22, 0);                      // aggregate calls not enabled yet
     uint64_t last = 0;
@@ -732,8 +779,8 @@ static void s8_refusals() {
         check_ks(Q, *k);
         s0 = stats(Q);
     };
-    auto refused = [&](int rc, int code) {
-        CHECK(rc == code && fz_last_error()[0]);
+    auto refused = [&](int rc, int code, const char *text = "") {        // (text: part of the refusal's own message)
+        CHECK(R(rc) == code && fz_last_error()[0] && strstr(fz_last_error(), text));
         const Stats s = stats(Q);
         CHECK(s.calls == s0.calls && s.batches == s0.batches && s.rows == s0.rows);
         accepted();
@@ -762,15 +809,28 @@ static void s8_refusals() {
     seeds = k->seeds;
     CHECK(off[3] > 0);
     refused(ks(seeds.data(), 3, nullptr, off.data(), &t), FZ_E_BADARG);
+    // two faults in one call: the rules are tested row by row, so the fault in the earlier row names the refusal (S11 pins these)
+    const std::string text30(30, 'x');
+    seeds = k->seeds;
+    seeds[0] = ~0ull;
+    off = {0, 10, 20, 19};
+    refused(ks(seeds.data(), 3, text30.data(), off.data(), &t), FZ_E_UNSUPPORTED, "seed 2^64 - 1");
+    seeds = k->seeds;
+    seeds[2] = ~0ull;
+    off = {0, 10, 9, 30};
+    refused(ks(seeds.data(), 3, text30.data(), off.data(), &t), FZ_E_BADARG, "message offsets must not decrease");
+    seeds = k->seeds;
+    off = {1, 10, 20, 30};
+    refused(ks(seeds.data(), 0, text30.data(), off.data(), &t), FZ_E_BADARG, "between 1 and max_rows");
     CHECK(t == 999);
 
     std::unique_ptr<AG> a = make_ag(3, 64), v = make_vf(3, 64, false);
     refused(submit_rc(Q, *a), FZ_E_BADARG);              // before fz_queue_enable_aggregate
     refused(submit_rc(Q, *v), FZ_E_BADARG);
-    CHECK(fz_queue_enable_aggregate(nullptr, BETA_VF, OMEGA_VF, 64, 1) == FZ_E_BADARG);
-    CHECK(fz_queue_enable_aggregate(Q, -1, OMEGA_VF, 64, 1) == FZ_E_BADARG && fz_queue_enable_aggregate(Q, BETA_VF, -1, 64, 1) == FZ_E_BADARG);
-    CHECK(fz_queue_enable_aggregate(Q, BETA_VF, OMEGA_VF, 0, 1) == FZ_E_BADARG);
-    for (int th : {0, 257}) CHECK(fz_queue_enable_aggregate(Q, BETA_VF, OMEGA_VF, 64, th) == FZ_E_BADARG);
+    CHECK(R(fz_queue_enable_aggregate(nullptr, BETA_VF, OMEGA_VF, 64, 1)) == FZ_E_BADARG);
+    CHECK(R(fz_queue_enable_aggregate(Q, -1, OMEGA_VF, 64, 1)) == FZ_E_BADARG && R(fz_queue_enable_aggregate(Q, BETA_VF, -1, 64, 1)) == FZ_E_BADARG);
+    CHECK(R(fz_queue_enable_aggregate(Q, BETA_VF, OMEGA_VF, 0, 1)) == FZ_E_BADARG);
+    for (int th : {0, 257}) CHECK(R(fz_queue_enable_aggregate(Q, BETA_VF, OMEGA_VF, 64, th)) == FZ_E_BADARG);
     refused(submit_rc(Q, *a), FZ_E_BADARG);              // a refused enable enables nothing
     CHECK(fz_queue_enable_aggregate(Q, BETA_VF, OMEGA_VF, 64, 1) == FZ_OK);
     for (int verify = 0; verify < 2; ++verify) {
@@ -797,6 +857,10 @@ static void s8_refusals() {
         refused(ag(x.vk.data(), nullptr, x.off.data(), 3, x.src(), 0, &t), FZ_E_BADARG);
         for (int flags : {FZ_QUEUE_KEEP_SK, FZ_QUEUE_DISCARD, FZ_QUEUE_ROWS_ON_DEVICE | FZ_QUEUE_DISCARD, 8})
             refused(ag(x.vk.data(), x.msgs.data(), x.off.data(), 3, x.src(), flags, &t), FZ_E_BADARG);
+        off = x.off;                                     // two faults in one call (S11 pins these)
+        off[0] = 1;
+        refused(ag(x.vk.data(), x.msgs.data(), off.data(), 0, x.src(), 0, &t), FZ_E_BADARG, "between 1 and max_rows");
+        refused(ag(x.vk.data(), nullptr, x.off.data(), 3, x.src(), 8, &t), FZ_E_BADARG, "h_msgs is NULL");
         CHECK(x.verdict == VERDICT_SENTINEL && t == 999);
     }
     refused(fz_queue_submit_verify(Q, v->vk.data(), v->msgs.data(), v->off.data(), 3, v->src(), nullptr, 0, &t), FZ_E_BADARG);
@@ -806,8 +870,12 @@ static void s8_refusals() {
     submit(Q, *v);
     CHECK(v->ticket == ++last);
     check_ag(Q, *v);
-    CHECK(fz_queue_wait(nullptr, 1, nullptr) == FZ_E_BADARG && fz_queue_release(nullptr, 1) == FZ_E_BADARG && fz_queue_drain(nullptr) == FZ_E_BADARG);
-    CHECK(fz_queue_stats(nullptr, nullptr, nullptr, nullptr) == FZ_E_BADARG && fz_queue_destroy(nullptr) == FZ_OK);
+    CHECK(R(fz_queue_wait(nullptr, 1, nullptr)) == FZ_E_BADARG && R(fz_queue_release(nullptr, 1)) == FZ_E_BADARG && R(fz_queue_drain(nullptr)) == FZ_E_BADARG);
+    CHECK(R(fz_queue_stats(nullptr, nullptr, nullptr, nullptr)) == FZ_E_BADARG && fz_queue_destroy(nullptr) == FZ_OK);
+    for (uint64_t unknown : {(uint64_t)0, last + 1}) {   // (S4 checks these codes; here their texts are on record)
+        CHECK(R(fz_queue_wait(Q, unknown, nullptr)) == FZ_E_BADARG && R(fz_queue_release(Q, unknown)) == FZ_E_BADARG);
+    }
+    CHECK(R(fz_queue_release_after(Q, last, nullptr)) == FZ_E_BADARG);
     CHECK(fz_queue_destroy(Q) == FZ_OK);
 }
 
@@ -911,9 +979,292 @@ static void s10_races(int per_thread) {
     CHECK(fz_queue_destroy(Q) == FZ_OK);
 }
 
+// ---- S11: a failing allocation -- in fz_queue_create, and in a batch on a cold worker ----------------------------------
+// The stub's control fails allocations [at, at + 2): fz_malloc tries a failed hipMalloc once more, so two in a row fail one fz_malloc.
+static long allocs_now() { std::lock_guard<std::mutex> g(g_log_mu); return g_allocs; }
+static void fail_allocs(long at) { std::lock_guard<std::mutex> g(g_log_mu); g_fail_at = at; g_fail_n = at < 0 ? 1 : 2; }
+static long s11_create() {
+    long a0, e0, st0, a1, e1, st1;
+    stub_live(&a0, &e0, &st0);
+    const long base = allocs_now();
+    fz_queue *Q = nullptr;
+    CHECK(fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), 2, 16, &Q) == FZ_OK && Q);
+    const long total = allocs_now() - base;
+    CHECK(total > 0 && fz_queue_destroy(Q) == FZ_OK);
+    tdump(false);                                        // (two workers close side by side: no fixed order to print)
+    for (long i = 0; i < total; ++i) {
+        g_quiet = i != total - 1;                        // the trace holds the last one: the first worker whole, the second without its matrix
+        fz_set_error(FZ_OK, "%s", "");
+        fail_allocs(allocs_now() + i);
+        Q = (fz_queue *)&a0;
+        const int rc = fz_queue_create(0, &g_P, RANK, BETA_SK, OMEGA_SK, g_A.data(), 2, 16, &Q);
+        fail_allocs(-1);
+        tdump();
+        CHECK(R(rc) != FZ_OK && fz_last_error()[0] && !Q);
+        stub_live(&a1, &e1, &st1);
+        CHECK(a1 == a0 && e1 == e0 && st1 == st0);
+    }
+    return total;
+}
+enum { FLOW_KS, FLOW_AG, FLOW_VF };
+struct Cell {
+    std::vector<std::unique_ptr<KS>> ks;
+    std::vector<std::unique_ptr<AG>> ag;
+    explicit Cell(int flow) {
+        if (flow == FLOW_KS) { ks.push_back(make_ks(3, 0)); ks.push_back(make_ks(2, FZ_QUEUE_KEEP_SK)); ks.push_back(make_ks(4, FZ_QUEUE_DISCARD)); }
+        else for (size_t n : {3, 1, 4}) ag.push_back(flow == FLOW_VF ? make_vf(n, 64, n == 1) : make_ag(n, 64));
+    }
+    void submit_all(fz_queue *Q) { for (auto &k : ks) submit(Q, *k); for (auto &x : ag) submit(Q, *x); }
+    void check_all(fz_queue *Q) { for (auto &k : ks) check_ks(Q, *k); for (auto &x : ag) check_ag(Q, *x); }
+};
+// the allocations one batch of `flow` makes on a cold worker behind Hold (whose one-row call has grown the keygen-sign scratch)
+static long s11_count(int flow) {
+    fz_queue *Q = mkq(1, 64);
+    Hold h(Q);
+    Cell c(flow);
+    const long base = allocs_now();
+    c.submit_all(Q);
+    h.open();
+    for (auto &k : c.ks) CHECK(fz_queue_wait(Q, k->ticket, nullptr) == FZ_OK);
+    for (auto &x : c.ag) CHECK(fz_queue_wait(Q, x->ticket, nullptr) == FZ_OK);
+    const long total = allocs_now() - base;
+    c.check_all(Q);
+    CHECK(total > 0 && fz_queue_destroy(Q) == FZ_OK);
+    return total;
+}
+static void s11_cell(int flow, long i) {
+    fz_queue *Q = mkq(1, 64);
+    Hold h(Q);
+    Cell c(flow);
+    const long before = live_allocs();
+    const size_t mark = stub_mark();
+    fail_allocs(allocs_now() + i);
+    c.submit_all(Q);
+    h.open();
+    int worker_tid = -1;
+    auto failed = [&](uint64_t ticket) {
+        fz_queue_result r;
+        memset(&r, 0xff, sizeof(r));
+        CHECK(F("wait", fz_queue_wait(Q, ticket, &r)) == FZ_E_HIP && strstr(fz_last_error(), "queued batch failed"));
+        CHECK(r.status == FZ_E_HIP && !r.d_vk && !r.d_sig && !r.d_sk_hat);
+    };
+    for (int k = 0; k < 2 && flow == FLOW_KS; ++k) failed(c.ks[k]->ticket);
+    for (auto &x : c.ag) failed(x->ticket);
+    if (flow == FLOW_KS) {                               // the discarded call: its failure surfaces once, in drain
+        CHECK(fz_queue_wait(Q, c.ks[2]->ticket, nullptr) == FZ_OK);
+        CHECK(F("drain", fz_queue_drain(Q)) == FZ_E_HIP && strstr(fz_last_error(), "a discarded call failed"));
+    }
+    CHECK(fz_queue_drain(Q) == FZ_OK);
+    fail_allocs(-1);
+    for (auto &k : c.ks) CHECK(k->vk_out == std::vector<int32_t>(k->n() * 2 * D, VK_SENTINEL));
+    for (auto &x : c.ag) CHECK(x->verdict == VERDICT_SENTINEL && x->agg_out == std::vector<int32_t>(RANK * D, AGG_SENTINEL));
+    // every copy that read a caller's rows is behind a synchronise of its stream on the worker's thread
+    const std::vector<Call> log = stub_log(mark);
+    for (const Call &r : log) if (r.fn == "hipMalloc failed") worker_tid = r.tid;
+    CHECK(worker_tid >= 0 && worker_tid != stub_tid());
+    for (auto &x : c.ag)
+        for (const Call &r : log) {
+            if (r.fn != "hipMemcpyAsync" || r.src != x->src()) continue;
+            bool drained = false;
+            for (const Call &s : log) drained |= s.fn == "hipStreamSynchronize" && s.stream == r.stream && s.seq > r.seq && s.tid == worker_tid;
+            CHECK(drained);
+        }
+    for (int k = 0; k < 2 && flow == FLOW_KS; ++k) CHECK(fz_queue_release(Q, c.ks[k]->ticket) == FZ_OK);
+    for (auto &x : c.ag) CHECK(fz_queue_release(Q, x->ticket) == FZ_OK);
+    flush(Q);
+    // What the batch took is back.  A keygen-sign batch replaces scratch the holding call had grown, and the flush grows the one
+    // area that was lost again: the count is the one before the batch.  The aggregate scratch was cold: the i areas fitted
+    // before the failing one stay the worker's scratch (as after a batch that succeeds), and nothing else does.
+    CHECK(live_allocs() == before + (flow == FLOW_KS ? 0 : i));
+    Hold again(Q);                                       // the same batch again is right
+    c.submit_all(Q);
+    again.open();
+    c.check_all(Q);
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+}
+static void s11_alloc() {
+    const long create = s11_create();
+    long n[3];
+    for (int flow : {FLOW_KS, FLOW_AG, FLOW_VF}) {
+        g_quiet = true;
+        n[flow] = s11_count(flow);
+        tdump();
+        for (long i = 0; i < n[flow]; ++i) {
+            // the trace holds two cells: the second block of a kept batch (the first goes back), an area in the middle of the aggregate scratch
+            g_quiet = !((flow == FLOW_KS && i == 3) || (flow == FLOW_AG && i == 5));
+            if (g_trace && !g_quiet) printf("# %s, allocation %ld of the batch fails\n", flow == FLOW_KS ? "keygen-sign" : "aggregate-verify", i);
+            s11_cell(flow, i);
+        }
+    }
+    g_quiet = false;
+    if (!g_trace) printf("S11 allocations: create %ld, keygen-sign %ld, aggregate-verify %ld, verify %ld\n", create, n[0], n[1], n[2]);
+}
+
+// ---- the recorded trace: fixed one-worker flows, one line per event (tests/golden/queue_runtime_trace.txt) ----------------
+// A flow keeps one thread at a time busy (Hold, waits, flush), so the order of the two logs does not depend on timing.
+static void t_idle() {
+    printf("# flow 1: create, enable and destroy an idle queue\n");
+    fz_queue *Q = mkq(1, 64);
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+}
+static void t_flags() {
+    printf("# flow 2: the S3 batches, cold scratch then warm\n");
+    fz_queue *Q = mkq(1, 64);
+    for (int round = 0; round < 2; ++round) {
+        for (int part = 0; part < 2; ++part) {
+            printf("# round %d, %s\n", round, part ? "a batch nobody keeps" : "mixed flags");
+            Hold h(Q);
+            std::vector<std::unique_ptr<KS>> c;
+            if (part == 0) for (int flags : {0, FZ_QUEUE_KEEP_SK, FZ_QUEUE_DISCARD, FZ_QUEUE_DISCARD | FZ_QUEUE_KEEP_SK}) c.push_back(make_ks(3 + c.size(), flags));
+            else for (int flags : {FZ_QUEUE_DISCARD, FZ_QUEUE_DISCARD | FZ_QUEUE_KEEP_SK, FZ_QUEUE_DISCARD}) c.push_back(make_ks(20 + c.size(), flags));
+            for (auto &k : c) submit(Q, *k);
+            h.open();
+            for (auto &k : c) check_ks(Q, *k);
+            CHECK(fz_queue_drain(Q) == FZ_OK);
+            flush(Q);
+            tdump();
+        }
+    }
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+}
+static void t_grow() {
+    printf("# flow 3: batches that grow the scratch, 4 rows then 40\n");
+    fz_queue *Q = mkq(1, 64);
+    for (size_t n : {4, 40}) {
+        Hold h(Q);
+        std::unique_ptr<KS> k = make_ks(n, FZ_QUEUE_DISCARD);
+        submit(Q, *k);
+        h.open();
+        check_ks(Q, *k);
+        tdump();
+    }
+    for (size_t n : {4, 40})
+        for (int verify = 0; verify < 2; ++verify) {
+            std::unique_ptr<AG> a = verify ? make_vf(n, 64, false) : make_ag(n, 64);
+            submit(Q, *a);
+            check_ag(Q, *a);
+            tdump();
+        }
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+}
+static void t_aggregate() {
+    for (int threads : {1, 4}) {
+        printf("# flow 4: the aggregate batch of S9, G = 9, host_threads %d\n", threads);
+        fz_queue *Q = mkq(1, 64, 64, threads);
+        Hold h(Q);
+        std::vector<std::unique_ptr<AG>> a;
+        for (size_t g = 0; g < 9; ++g) {
+            const int flags = g % 2 ? FZ_QUEUE_ROWS_ON_DEVICE : 0;
+            a.push_back(g % 3 == 2 ? make_vf(g + 1, 64, g == 5, flags) : make_ag(g + 1, 64, flags));
+            a.back()->want_agg = g != 3;
+            a.back()->want_verdict = a.back()->verify_only || g != 4;
+        }
+        for (auto &x : a) submit(Q, *x);
+        h.open();
+        for (auto &x : a) CHECK(fz_queue_wait(Q, x->ticket, nullptr) == FZ_OK);      // (the callers' device rows are freed once the worker is idle)
+        for (auto &x : a) check_ag(Q, *x);
+        CHECK(fz_queue_destroy(Q) == FZ_OK);
+        tdump();
+    }
+}
+static void t_failing_steps() {
+    printf("# flow 5: one failing step of each kind\n");
+    fz_queue *Q = mkq(1, 64);
+    const int codes[3] = {FZ_E_HIP, FZ_E_UNSUPPORTED, FZ_E_BADARG};
+    int injected = 0;
+    for (int entry : {E_SAMPLE, E_KEYGEN, E_CHAL, E_SIGN}) {
+        printf("# keygen-sign, %s fails\n", ENTRY[entry]);
+        Hold h(Q);
+        arm(entry, entry == E_SAMPLE ? 0 : 1, codes[injected % 3], "injected failure #" + std::to_string(injected));
+        ++injected;
+        Cell c(FLOW_KS);
+        c.submit_all(Q);
+        h.open();
+        for (int k = 0; k < 2; ++k) CHECK(F("wait", fz_queue_wait(Q, c.ks[k]->ticket, nullptr)) != FZ_OK);
+        CHECK(fz_queue_wait(Q, c.ks[2]->ticket, nullptr) == FZ_OK);
+        CHECK(F("drain", fz_queue_drain(Q)) != FZ_OK && fz_queue_drain(Q) == FZ_OK);
+        for (int k = 0; k < 2; ++k) CHECK(fz_queue_release(Q, c.ks[k]->ticket) == FZ_OK);
+        disarm();
+        flush(Q);
+        tdump();
+    }
+    // (the verify flow shares its first steps with the aggregate flow: S6 fails each of them, the trace holds the one that is its own)
+    const std::pair<int, int> steps[6] = {{FLOW_AG, E_CHAL}, {FLOW_AG, E_NTT}, {FLOW_AG, E_RAGGED}, {FLOW_AG, E_VPART}, {FLOW_AG, E_REDUCE}, {FLOW_VF, E_VTGT}};
+    for (const auto &step : steps) {
+        const int flow = step.first, entry = step.second;
+        printf("# %s, %s fails\n", flow == FLOW_VF ? "verify" : "aggregate-verify", ENTRY[entry]);
+        Hold h(Q);
+        arm(entry, entry == E_CHAL ? 1 : 0, codes[injected % 3], "injected failure #" + std::to_string(injected));
+        ++injected;
+        Cell c(flow);
+        c.submit_all(Q);
+        h.open();
+        for (auto &x : c.ag) CHECK(F("wait", fz_queue_wait(Q, x->ticket, nullptr)) != FZ_OK);
+        CHECK(fz_queue_drain(Q) == FZ_OK);
+        for (auto &x : c.ag) CHECK(fz_queue_release(Q, x->ticket) == FZ_OK);
+        disarm();
+        flush(Q);
+        tdump();
+    }
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+    printf("# a failing allocation: in create, then in each batch (S11)\n");
+    s11_alloc();
+}
+static void t_release() {
+    printf("# flow 6: release, release_after with one consumer, release of a released ticket\n");
+    hipStream_t cs;
+    fz_ctx *cons = consumer(&cs);
+    g_consumer_streams.insert(cs);
+    fz_queue *Q = mkq(1, 64);
+    Hold h(Q);
+    std::vector<std::unique_ptr<KS>> c;
+    c.push_back(make_ks(3, 0)); c.push_back(make_ks(2, FZ_QUEUE_KEEP_SK));
+    for (auto &k : c) submit(Q, *k);
+    h.open();
+    for (auto &k : c) check_ks(Q, *k, false);
+    CHECK(fz_queue_release(Q, c[0]->ticket) == FZ_OK);
+    CHECK(fz_queue_release_after(Q, c[1]->ticket, cons) == FZ_OK);
+    flush(Q);
+    tdump();
+    printf("# released before\n");
+    CHECK(fz_queue_release(Q, c[0]->ticket) == FZ_OK && fz_queue_release_after(Q, c[1]->ticket, cons) == FZ_OK);
+    flush(Q);
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+    consumer_destroy(cons, cs);
+    tdump();
+    g_consumer_streams.clear();
+}
+static void t_destroy() {
+    printf("# flow 7: destroy with two results unreleased\n");
+    fz_queue *Q = mkq(1, 64);
+    Hold h(Q);
+    std::vector<std::unique_ptr<KS>> c;
+    c.push_back(make_ks(3, 0)); c.push_back(make_ks(2, FZ_QUEUE_KEEP_SK));
+    for (auto &k : c) submit(Q, *k);
+    h.open();
+    for (auto &k : c) check_ks(Q, *k, false);
+    CHECK(fz_queue_destroy(Q) == FZ_OK);
+    tdump();
+}
+
 int main(int argc, char **argv) {
     setenv("FZ_POOL_MB", "0", 1);                        // every fz_free is a hipFree
     for (int i = 0; i < RANK * D; ++i) g_A.push_back(1 + md((int64_t)(mix(777 + (uint64_t)i) >> 2)) % (int32_t)(MQ - 1));
+    g_caller_tid = stub_tid();
+    if (argc > 1 && !strcmp(argv[1], "trace")) {
+        g_trace = true;
+        t_idle(); t_flags(); t_grow(); t_aggregate(); t_failing_steps(); t_release(); t_destroy();
+        printf("# the refusals of S8\n");
+        s8_refusals();
+        printf("# end\n");
+        return 0;
+    }
     long a0, e0, st0, a1, e1, st1;
     stub_live(&a0, &e0, &st0);
     s1_cut();        printf("S1 ok\n");
@@ -926,6 +1277,7 @@ int main(int argc, char **argv) {
     s8_refusals();   printf("S8 ok\n");
     s9_aggregate();  printf("S9 ok\n");
     s10_races(argc > 1 ? atoi(argv[1]) : 50); printf("S10 ok\n");
+    s11_alloc();     printf("S11 ok\n");
     stub_live(&a1, &e1, &st1);
     CHECK(a1 == a0 && e1 == e0 && st1 == st0);           // every queue and context gave back what it took
     printf("done\n");
@@ -933,30 +1285,56 @@ int main(int argc, char **argv) {
 }
 '''
 
-SCENARIOS = ["S%d ok" % k for k in range(1, 11)]
+SCENARIOS = ["S%d ok" % k for k in range(1, 12)]
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "queue_runtime_trace.txt")
+PLAIN = "-fno-sanitize=all"                                   # the build without a sanitizer, in the place of a sanitizer's option
 
 
 def _run(tmp_path, san, name, env):
+    """-> (the scenarios' run, the trace's run) of one build"""
     toolchain()                                               # (skips without hipcc)
     if not sanitizer_links(tmp_path, san):
         pytest.skip("the runtime of %s is not available" % san)
     exe = build_driver(tmp_path, UNITS, DRIVER, san, name=name, sources=[os.path.join(CSRC, "fz_host.cpp")],
                        flags=["-fno-sanitize-recover=all"] if "address" in san else [])
-    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=dict(os.environ, FZ_POOL_MB="0", **env))
+    env = dict(os.environ, FZ_POOL_MB="0", **env)
+    return [subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=300, env=env) for args in ([], ["trace"])]
+
+
+def _same_trace(r):
+    """the trace of this build is the recorded one (tests/golden: recorded from the unit before its steps were written once)"""
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    got = r.stdout.splitlines()
+    with open(GOLDEN) as fh:
+        want = fh.read().splitlines()
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, "trace line %d: got %r, recorded %r (after %r)" % (k + 1, g, w, got[max(0, k - 3):k])
+    assert len(got) == len(want) and got[-1] == "# end", "the trace has %d lines, the recorded one %d" % (len(got), len(want))
 
 
 def test_queue_under_asan_ubsan_and_leak_detection(tmp_path):
-    r = _run(tmp_path, "-fsanitize=address,undefined", "queue_asan",
-             dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    r, t = _run(tmp_path, "-fsanitize=address,undefined", "queue_asan",
+                dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     assert [ln for ln in r.stdout.splitlines() if ln.endswith(" ok")] == SCENARIOS and r.stdout.splitlines()[-1] == "done"
+    assert "ERROR" not in t.stderr and "runtime error" not in t.stderr, t.stderr[-3000:]
+    _same_trace(t)
 
 
 def test_queue_under_tsan(tmp_path):
-    r = _run(tmp_path, "-fsanitize=thread", "queue_tsan", dict(TSAN_OPTIONS="halt_on_error=0:report_signal_unsafe=0"))
+    r, t = _run(tmp_path, "-fsanitize=thread", "queue_tsan", dict(TSAN_OPTIONS="halt_on_error=0:report_signal_unsafe=0"))
     if "FATAL: ThreadSanitizer" in r.stderr and "unexpected memory mapping" in r.stderr:
         pytest.skip("ThreadSanitizer cannot map its shadow memory in this container")
     assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     assert [ln for ln in r.stdout.splitlines() if ln.endswith(" ok")] == SCENARIOS and r.stdout.splitlines()[-1] == "done"
+    assert "WARNING: ThreadSanitizer" not in t.stderr, t.stderr[-4000:]
+    _same_trace(t)
+
+
+def test_queue_trace_without_a_sanitizer(tmp_path):
+    r, t = _run(tmp_path, PLAIN, "queue_plain", {})
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    assert [ln for ln in r.stdout.splitlines() if ln.endswith(" ok")] == SCENARIOS and r.stdout.splitlines()[-1] == "done"
+    _same_trace(t)
