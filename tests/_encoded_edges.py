@@ -14,7 +14,8 @@ rows, bound), not of a security parameter -- with the contexts, rows, fields and
 Everything is Python integers or int64 numpy; the transforms are the reference loops (oracle.py_ntt_forward / py_ntt_inverse) with
 the same tables the context is given, each distinct row transformed once.  The bytes are spec_pack / spec_unpack of
 tests/test_encoding_host.py (functions of (B, w) alone).  tests/test_encoded_edges_host.py checks these fixtures on the CPU;
-tests/test_gpu_encoded_edges.py holds the kernels to them."""
+tests/test_gpu_encoded_edges.py holds the kernels to them, tests/test_gpu_many_encoded_edges.py the many-committee kernels
+(group_partials, group_targets, same_sign_inputs)."""
 import functools
 
 import numpy as np
@@ -171,6 +172,39 @@ def aggregate_partial(spec, n, z, alpha, skip=None):
     return prod.sum(axis=0).astype(np.int64).reshape(z.shape[1:])
 
 
+def group_bounds(sizes):
+    """[(first, one past the last)] record of every group of consecutive records"""
+    off = np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))])
+    return [(int(a), int(b)) for a, b in zip(off, off[1:])]
+
+
+def group_partials(spec, n, z, alpha, sizes, skip=None):
+    """[G][l][n] int64: aggregate_partial of every group of sizes[g] consecutive records of z [N][l][n] / alpha [N][n] / skip [N];
+    a group with no kept record (none at all, or every one skipped) gives zeros"""
+    z, alpha = np.asarray(z, dtype=np.int64), np.asarray(alpha, dtype=np.int64)
+    assert sum(sizes) == z.shape[0] == alpha.shape[0] and (skip is None or len(skip) == z.shape[0])
+    out = np.zeros((len(sizes),) + z.shape[1:], dtype=np.int64)
+    for g, (a, b) in enumerate(group_bounds(sizes)):
+        sk = None if skip is None else np.asarray(skip)[a:b]
+        if b > a and (sk is None or (sk == 0).any()):
+            out[g] = aggregate_partial(spec, n, z[a:b], alpha[a:b], sk)
+    return out
+
+
+def group_targets(spec, vk, c_hat, alpha, sizes, skip=None):
+    """[G][n] int64: per group of sizes[g] consecutive signers the sum, over those with skip[i] == 0, of
+    cent(keyed_target(spec, vk_i, c_i) * alpha_i); vk [N][2][n], c_hat / alpha [N][n] any int32 (every factor is below 2^31 in
+    size: the products fit int64).  The kernels' target partials are these sums modulo q only"""
+    q = modulus(spec)
+    term = cent(keyed_target(spec, vk, c_hat) * np.asarray(alpha, dtype=np.int64), q)
+    assert sum(sizes) == term.shape[0] and (skip is None or len(skip) == term.shape[0])
+    keep = np.ones(term.shape[0], dtype=bool) if skip is None else np.asarray(skip) == 0
+    out = np.zeros((len(sizes), term.shape[1]), dtype=np.int64)
+    for g, (a, b) in enumerate(group_bounds(sizes)):
+        out[g] = term[a:b][keep[a:b]].sum(axis=0)
+    return out
+
+
 def verify_sums(spec, n, z, A):
     """[N][n] centred: cent(sum_k A_k (.) NTT(z_k)); z [N][l][n], A [l][n] any int32"""
     q = modulus(spec)
@@ -270,6 +304,24 @@ def key_inputs(count, n, seed):
         vk[i] = rng.integers(I32_MIN, I32_MAX + 1, size=(2, n), dtype=np.int64)
         ch[i] = rng.integers(I32_MIN, I32_MAX + 1, size=n, dtype=np.int64)
     return vk, ch
+
+
+def same_sign_inputs(spec, n, l, N, B, sign):
+    """(z [N][l][n], alpha [N][n]) on a root context with a prime modulus: every product cent(NTT(z_i) (.) alpha_i) is exactly
+    sign * h, h = (q - 1) / 2, so every partial of a group of N_g signers is sign * N_g * h -- the largest sum N_g signers can
+    leave.  A record is l copies of one of five random rows with |z| <= B whose forward coefficients are all units, and
+    alpha_i = cent(sign * h * NTT(z_i)^-1)"""
+    q, h = modulus(spec), half(spec)
+    assert spec[1] == "root" and sign in (1, -1)         # (the inverses are Fermat's: the products are checked below)
+    rng = np.random.default_rng(n + l + q % 1000)
+    pool = rng.integers(-B, B + 1, size=(5, n), dtype=np.int64)
+    F = forward(spec, n, pool)
+    assert (F % q != 0).all(), "a forward coefficient is 0 mod q: it has no inverse"
+    inv = np.array([[pow(int(v) % q, q - 2, q) for v in row] for row in F], dtype=object)
+    alpha = cent(np.array((sign * h * inv) % q, dtype=np.int64), q)
+    assert (cent(F * alpha, q) == sign * h).all() and I32_MIN <= alpha.min() and alpha.max() <= I32_MAX
+    idx = np.arange(N) % 5
+    return np.repeat(pool[idx][:, None, :], l, axis=1), alpha[idx]
 
 
 def solve_right_key(spec, vk, c_hat, sums):

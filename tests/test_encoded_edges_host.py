@@ -3,7 +3,9 @@ digests, the coverage the GPU module (tests/test_gpu_encoded_edges.py) rests on 
 at or above 2^31 of both context kinds, every field width 2 .. 32 -- the canonicity of every decoder-side record, the exact
 maxima of the encoder-side ones, and a replay of the kernels' arithmetic with fz_arith.h built for the host: mulacc16's step at
 its operand bounds, and the forward passes with the 4-op multiply put in the 6-op form's place at a modulus that is not fast,
-which changes the fixtures' expectations (so the kernels doing the same would be caught)."""
+which changes the fixtures' expectations (so the kernels doing the same would be caught).  For the many-committee module
+(tests/test_gpu_many_encoded_edges.py): the per-group spec against the single-group one, the sums of one sign at exactly
++-N_g (q - 1) / 2, and that module's own case lists held to the same coverage."""
 import ctypes
 import hashlib
 import json
@@ -183,6 +185,88 @@ def test_multipliers_carry_the_int32_extremes():
         moved = sums.copy()
         moved[3, n - 1] += 1
         assert X.verdicts(spec, sums, moved).tolist() == [0, 0, 0, 3, 0]
+
+
+# ---- the many-committee fixtures (tests/test_gpu_many_encoded_edges.py) ----------------------------------------------------------
+def test_group_partials_and_targets_are_the_single_group_spec_per_group():
+    spec, n, l = ("top", "root"), 64, 2
+    q = X.modulus(spec)
+    z = X.records_of(X.decoder_rows(spec, n)[1], l, 5)[np.arange(9) % 5]
+    alpha = X.multipliers(9, n, 1)
+    vk, c = X.key_inputs(9, n, 2)
+    assert np.array_equal(X.group_partials(spec, n, z, alpha, [9])[0], X.aggregate_partial(spec, n, z, alpha))
+    skip = np.where(np.arange(9) % 3 == 0, 6, 0).astype(np.int32)
+    keep = skip == 0
+    got = X.group_partials(spec, n, z, alpha, [9], skip)
+    assert got.shape == (1, l, n) and got.dtype == np.int64
+    assert np.array_equal(got[0], X.aggregate_partial(spec, n, z[keep], alpha[keep])) and not np.array_equal(got[0], X.aggregate_partial(spec, n, z, alpha))
+    # several groups: an empty one and one whose every signer is skipped give zeros, the others their own records' sums
+    sizes, skip = [0, 4, 2, 3], np.array([0, 6, 0, 0, 3, 3, 0, 0, 6], dtype=np.int32)
+    got, tgt = X.group_partials(spec, n, z, alpha, sizes, skip), X.group_targets(spec, vk, c, alpha, sizes, skip)
+    assert got.shape == (4, l, n) and tgt.shape == (4, n) and tgt.dtype == np.int64
+    assert not (got[0].any() or got[2].any() or tgt[0].any() or tgt[2].any())
+    assert np.array_equal(got[1], X.aggregate_partial(spec, n, z[[0, 2, 3]], alpha[[0, 2, 3]]))
+    assert np.array_equal(got[3], X.aggregate_partial(spec, n, z[[6, 7]], alpha[[6, 7]]))
+    assert np.array_equal(X.group_partials(spec, n, z, alpha, sizes, np.full(9, 6))[1:], np.zeros((3, l, n), dtype=np.int64))
+    # the targets in Python integers, signer by signer
+    for g, members in ((1, [0, 2, 3]), (3, [6, 7])):
+        for j in (0, n // 2, n - 1):
+            want = sum(E.cent(E.cent(int(vk[i, 0, j]) * int(c[i, j]) + int(vk[i, 1, j]), q) * int(alpha[i, j]), q) for i in members)
+            assert int(tgt[g, j]) == want
+    assert np.array_equal(X.group_targets(spec, vk, c, alpha, [9])[0], X.group_targets(spec, vk, c, alpha, [4, 5]).sum(axis=0))
+
+
+def test_same_sign_inputs_leave_the_largest_sums(lib):
+    import test_gpu_many_encoded_edges as M
+    assert M.SAME_SIGN_SPECS == [(k, "root") for k in E.ROOT_MODULI] + [("top", "root")]
+    for spec in M.SAME_SIGN_SPECS:
+        q, h = X.modulus(spec), X.half(spec)
+        assert all(pow(a, q - 1, q) == 1 for a in (2, 3, 5, 7))
+        for n in X.DEGREES:
+            l, B, sizes = M._agg_ls(n)[1], M.SAME_SIGN_BOUNDS[n], [67, 1, 33]
+            for sign in (1, -1):
+                z, alpha = X.same_sign_inputs(spec, n, l, sum(sizes), B, sign)
+                assert z.shape == (101, l, n) and np.abs(z).max() <= B and not X.encoded(z, B)[1].any()
+                assert alpha.shape == (101, n) and E.I32_MIN <= alpha.min() and alpha.max() <= E.I32_MAX
+                assert len({r.tobytes() for r in z[:, 0]}) == 5 and (z == z[:, :1]).all()
+                got = X.group_partials(spec, n, z, alpha, sizes)
+                for g, ng in enumerate(sizes):
+                    assert (got[g] == sign * ng * h).all(), (spec, n, sign, g)
+                assert np.array_equal(X.group_partials(spec, n, z[:67], alpha[:67], [67])[0], got[0])
+                # one step of the kernels' sum, in their arithmetic: the product is exactly sign * h
+                assert lib.t_mulacc(float(X.forward(spec, n, z[3, 0])[5]), float(alpha[3, 5]), q) == sign * h
+
+
+def test_the_many_committee_cases_cover_both_forms_the_wide_moduli_and_every_width(lib):
+    import test_gpu_many_encoded_edges as M
+    assert sorted(M.CASES) == sorted((s, n) for s in X.SPECS for n in X.DEGREES) and len(M.CASES) == 38
+    assert sorted(M.A_CASES) == sorted((s, n, l) for s, n in M.CASES for l in M._agg_ls(n))
+    for n in X.DEGREES:
+        specs = [s for s, d in M.CASES if d == n]
+        assert {lib.t_fast(X.modulus(s)) for s in specs} == {0, 1}
+        assert len({X.modulus(s) for s in specs if X.modulus(s) >= 2 ** 31}) >= 4
+        assert {"odd", "q1", "root"} == {s[1] for s in specs}
+        # odd tables and a root's on both forms; the top tables (every entry q - 1) are on fast moduli only
+        assert {s[1] for s in specs if not lib.t_fast(X.modulus(s))} == {"odd", "root"}
+    assert all(X.width(X.half(s)) < 32 for s in X.SPECS if lib.t_fast(X.modulus(s)))           # no fast modulus holds a 32-bit field
+    # the seam: either form, either kind of context, either side of 2^31
+    assert {(lib.t_fast(X.modulus(s)), s[1] == "root", X.modulus(s) >= 2 ** 31) for s in M.SEAM_SPECS} == \
+        {(1, True, False), (0, True, True), (0, False, True), (1, False, False)}
+    # the width sweep
+    for n in X.DEGREES:
+        reach = {0: set(), 1: set()}
+        for s, d in M.SWEEP_CASES:
+            if d == n:
+                reach[lib.t_fast(X.modulus(s))] |= {w for w, B in X.SWEEP if s in X.sweep_specs(B)}
+        assert reach[1] == set(range(2, 32)) and reach[0] == set(range(2, 33))
+    assert set(M.MASKS) == {"none", "zeros", "thirds", "group", "all"} and [67, 1, 33] in M.SHAPES and [40, 1] in M.SHAPES
+    for sizes in M.SHAPES:
+        N = sum(sizes)
+        assert M.mask_of("none", sizes) is None and not M.mask_of("zeros", sizes).any() and M.mask_of("all", sizes).all()
+        g = M.mask_of("group", sizes)
+        a, b = X.group_bounds(sizes)[int(np.argmax(sizes))]
+        assert g[a:b].all() and int((g != 0).sum()) == b - a == max(sizes)
+        assert (M.mask_of("thirds", sizes) != 0).tolist() == [i % 3 == 0 for i in range(N)]
 
 
 # ---- the kernels' arithmetic on the host ---------------------------------------------------------------------------------------

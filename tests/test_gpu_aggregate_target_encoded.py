@@ -7,8 +7,11 @@ fz_aggregate_encoded_ragged_async for the aggregates' partials and d_out, and fz
 on the compacted non-skipped rows for the targets' partials (a call whose every signer is skipped has nothing to hand that oracle:
 the entry's contract says zero).  Both kinds of partials lie stride = width + 2 words apart inside 16 KiB guards of sentinels, as
 does d_out, and every word that is not an output is found as it was.  Contexts: the scheme's two parameter sets (the 4-op multiply)
-and q = 4294828033 at either degree (the 6-op multiply): all four instantiations run.  The scheme cases run the reference-made
-flows of tests/golden/scheme_many_*.  No tolerance anywhere."""
+and q = 4294828033 at either degree (the 6-op multiply).  All four instantiations run here, but the "top" contexts are compared with
+sibling kernels only -- the aggregates share aggregate_encoded_slice with their oracle, the targets agg_target4 with theirs, so a
+mistake in a shared piece cancels out; what these comparisons say is that both entries leave the same int64 words.  The kernels are
+held to the spec at the 6-op form, at moduli at or above 2^31 and at every field width in tests/test_gpu_many_encoded_edges.py.  The
+scheme cases run the reference-made flows of tests/golden/scheme_many_*.  No tolerance anywhere."""
 import functools
 import json
 import os
